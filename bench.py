@@ -14,7 +14,13 @@ DPS 16, nc_ddpmpp 64, CIFAR 128); the ns_step simulator runs independent replica
 GPU).  `--weak` (or an explicit per-GPU `--batch`) gives every rank the whole batch.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch 64] [--weak]
+    python bench.py --full ...                  # + every other phase, rooflines, CPU baselines
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K PC steps and prints the line; `--dump-outputs DIR`
+also writes the last timed step's x / x_mean as DIR/*.npy.  The other phases (rooflines, DSM /
+CIFAR / PINN training, DPS, ns_step, nc_ddpmpp, CPU baselines) run only with `--full`, and
+their keys of the line are absent or null without it.
 
 Rank 0 prints ONE JSON line.  value = score-net evals/s of the whole job.
 """
@@ -53,6 +59,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed PC steps also run every other phase: the dominant-kernel "
+                         "and upfirdn2d rooflines, DSM / CIFAR / PINN training, DPS, ns_step, "
+                         "nc_ddpmpp and the CPU baselines (each with its own --no-* / --*-steps "
+                         "switch); without it only the headline PC-sampler figure is measured")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed PC steps returned after the last one (x and x_mean "
+                         "of the global batch, float32) as DIR/x.npy and DIR/x_mean.npy")
     ap.add_argument("--global-batch", type=int, default=64,
                     help="configs[2] global batch, sharded global/N per GPU (strong scaling)")
     ap.add_argument("--weak", action="store_true",
@@ -1011,8 +1025,39 @@ def _plumbing(args, ctx):
         torch.distributed.destroy_process_group()
 
 
+def dump_outputs(path, arrays, cap=64 << 20):
+    """--dump-outputs: path/<name>.npy (float32) for every tensor of `arrays`; beyond `cap`
+    bytes in all, a fixed seeded sample of each tensor's flat elements (the same indices in
+    every run)."""
+    os.makedirs(path, exist_ok=True)
+    per = cap // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.size > per:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, per, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def advance(eng, model, n):
+    """n more PC steps; a run longer than the SDE's time grid (N = 1000 steps) restarts from a
+    fresh prior draw when the grid runs out (the step graph is kept)."""
+    while n > 0:
+        left = eng.sde.N - eng._done
+        if left == 0:
+            eng.reset(model)
+            continue
+        eng.advance(min(n, left))
+        n -= min(n, left)
+
+
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("[bench] --steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # the plain run: the headline PC-sampler figure and nothing else
+        args.no_roofline = args.no_train = args.no_pinn = args.no_dps = True
+        args.no_cpu_baseline = True
+        args.cifar_steps = args.ns_steps = args.ncddpmpp_steps = 0
     _heartbeat()
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -1045,13 +1090,13 @@ def main():
                             use_graph=not args.no_graph, dist_ctx=ctx if world > 1 else None)
     log(f"rank {ctx.rank}/{world}: model built, capturing PC step")
     eng.reset(model)
-    eng.advance(args.warmup)
+    advance(eng, model, args.warmup)
     log("warm-up done, timing PC steps")
     torch.cuda.synchronize(dev)
     ctx.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    eng.advance(args.steps)
+    advance(eng, model, args.steps)
     torch.cuda.synchronize(dev)
     ctx.barrier()
     torch.cuda.synchronize(dev)
@@ -1065,6 +1110,11 @@ def main():
     sums = None
     if args.sample_sums:
         sums = ctx.all_gather_cat(x.double().sum(dim=(1, 2, 3))).cpu().tolist()
+    if args.dump_outputs:  # what advance() returned after the last timed step, global sample order
+        outs = {"x": ctx.all_gather_cat(eng._x), "x_mean": ctx.all_gather_cat(eng._xm)}
+        if ctx.rank == 0:
+            dump_outputs(args.dump_outputs, outs)
+        del outs
 
     roof = None
     if ctx.rank == 0 and not args.no_roofline:

@@ -55,6 +55,34 @@ def test_mismatched_world_size_is_refused():
     assert rc == 2 and "refusing" in err and not out.strip()
 
 
+def test_full_and_dump_outputs_are_accepted():
+    rc, out, err = _run(["--gpus", "1", "--plumbing", "--full", "--dump-outputs", "unused"])
+    assert rc == 0, err[-2000:]
+    assert json.loads(out.strip())["n_gpus"] == 1
+
+
+def test_dump_outputs_float32_and_fixed_sample_beyond_the_cap(tmp_path):
+    """dump_outputs writes <name>.npy in float32; past the byte cap each array becomes a
+    seeded sample of its flat elements -- the same indices on every call, in order."""
+    code = ("import sys, torch, bench\n"
+            "arrs = {'a': torch.arange(100, dtype=torch.float64), 'b': torch.ones(2, 3)}\n"
+            "bench.dump_outputs(sys.argv[1], arrs, cap=int(sys.argv[2]))\n")
+    import numpy as np
+    got = {}
+    for tag, cap in (("whole", 1 << 20), ("s1", 80), ("s2", 80)):
+        d = str(tmp_path / tag)
+        p = subprocess.run([sys.executable, "-c", code, d, str(cap)], capture_output=True,
+                           text=True, timeout=240, cwd=REPO)
+        assert p.returncode == 0, p.stderr[-2000:]
+        got[tag] = {n: np.load(os.path.join(d, n + ".npy")) for n in ("a", "b")}
+    assert got["whole"]["a"].dtype == np.float32 and got["whole"]["b"].shape == (2, 3)
+    np.testing.assert_array_equal(got["whole"]["a"], np.arange(100, dtype=np.float32))
+    a = got["s1"]["a"]  # 80 bytes / (4 bytes x 2 arrays) = 10 elements each at the most
+    assert a.shape == (10,) and np.all(np.diff(a) > 0) and got["s1"]["b"].shape == (2, 3)
+    np.testing.assert_array_equal(a, got["s2"]["a"])
+    assert sum(v.nbytes for v in got["s1"].values()) <= 80
+
+
 def test_per_rank_of_gives_the_n_gpu_per_rank_batch():
     """--per-rank-of 8 on one process: every phase at the per-rank batch of the 8-GPU
     strong-scaled run (64 / 8 = 8 for configs[2])."""

@@ -356,11 +356,13 @@ def test_rccl_all_reduce_captures_in_a_hip_graph():
     np.testing.assert_array_equal(r[1], np.full(2, 3.0, np.float32))
 
 
-def test_bench_gpus_2_matches_world_1_samples():
+def test_bench_gpus_2_matches_world_1_samples(tmp_path):
     """`python bench.py --gpus 2` (gloo, both ranks on the one device) launches two ranks,
     shards the global batch (strong scaling, the configs[2] form: --global-batch 8 -> 4 per
     rank), reports n_gpus 2 and produces the samples of the single-rank run (Philox noise
-    keyed by the global sample index; the Langevin batch-mean norm summed over ranks)."""
+    keyed by the global sample index; the Langevin batch-mean norm summed over ranks).
+    --dump-outputs writes the last timed step's x / x_mean of the global batch (float32, global
+    sample order) in both launches, and a plain run (no --full) reports no other phase."""
     import json
     import subprocess
     bench = os.path.join(HERE, "..", "bench.py")
@@ -371,7 +373,8 @@ def test_bench_gpus_2_matches_world_1_samples():
     for n in (1, 2):
         env = dict(os.environ, BPK_DIST_BACKEND="gloo")
         env.pop("WORLD_SIZE", None)
-        p = subprocess.run([sys.executable, bench, "--gpus", str(n)] + common, env=env,
+        p = subprocess.run([sys.executable, bench, "--gpus", str(n), "--dump-outputs",
+                            str(tmp_path / f"n{n}")] + common, env=env,
                            capture_output=True, text=True, timeout=400)
         assert p.returncode == 0, p.stderr[-3000:]
         out[n] = json.loads(p.stdout.strip().splitlines()[-1])
@@ -381,3 +384,15 @@ def test_bench_gpus_2_matches_world_1_samples():
     a, b = np.array(out[1]["sample_sums"]), np.array(out[2]["sample_sums"])
     assert a.shape == b.shape == (8,)
     np.testing.assert_allclose(b, a, rtol=1e-5, atol=1e-3 * np.abs(a).max())
+    for n, sums in ((1, a), (2, b)):
+        assert out[n]["steps"] == 3 and out[n]["ms_per_step"] > 0
+        assert out[n]["roofline"] is None and "train_steps_per_s" not in out[n]
+        dumped = {k: np.load(tmp_path / f"n{n}" / f"{k}.npy") for k in ("x", "x_mean")}
+        for v in dumped.values():
+            assert v.dtype == np.float32 and v.shape == (8, 1, 128, 128) and np.isfinite(v).all()
+        # the dumped x_mean is the tensor the line's sample sums were taken from
+        np.testing.assert_allclose(dumped["x_mean"].astype(np.float64).sum(axis=(1, 2, 3)), sums,
+                                   rtol=1e-9, atol=1e-9 * 128 * 128 * np.abs(dumped["x_mean"]).max())
+        assert np.abs(dumped["x"] - dumped["x_mean"]).max() > 0  # x carries the last noise draw
+    d1, d2 = np.load(tmp_path / "n1" / "x_mean.npy"), np.load(tmp_path / "n2" / "x_mean.npy")
+    np.testing.assert_allclose(d2, d1, rtol=0, atol=1e-3 * np.abs(d1).max())

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of one environment switch over bench.py phases, interleaved.
 #   tools/gpu_ab.sh OUT VAR "VALUES" REPEATS [bench.py args...]
-# e.g. tools/gpu_ab.sh gpurun_out/ab BPK_GN_FANOUT "0 1" 2 --no-pinn --no-dps --ns-steps 0 \
+# e.g. tools/gpu_ab.sh OUT BPK_GN_FANOUT "0 1" 2 --full --no-pinn --no-dps --ns-steps 0 \
 #        --ncddpmpp-steps 0 --no-cpu-baseline --no-roofline --train-steps 8 --cifar-steps 6
 # The round's switches: BPK_DEFER_WGRAD, BPK_GN_FANOUT, BPK_IN_FANOUT, BPK_PINN_COPIES,
 # BPK_GN_CONV_AD_TRAIN.  Each run's JSON line goes to OUT/<VAR>_<value>_<repeat>.json and

@@ -5,10 +5,10 @@
 set -o pipefail
 O=${1:-gpurun_out/evidence}; mkdir -p $O; export TMPDIR=/tmp
 for r in 1 2; do
-  timeout -k 10 900 python3 bench.py > $O/bench_$r.json 2> $O/bench_$r.err || { tail -20 $O/bench_$r.err; exit 1; }
+  timeout -k 10 900 python3 bench.py --full > $O/bench_$r.json 2> $O/bench_$r.err || { tail -20 $O/bench_$r.err; exit 1; }
   grep -o '"value": [0-9.]*' $O/bench_$r.json | head -1
 done
-timeout -k 10 900 python3 bench.py --per-rank-of 8 > $O/per_rank_of_8.json 2> $O/per_rank_of_8.err || { tail -20 $O/per_rank_of_8.err; exit 1; }
+timeout -k 10 900 python3 bench.py --full --per-rank-of 8 > $O/per_rank_of_8.json 2> $O/per_rank_of_8.err || { tail -20 $O/per_rank_of_8.err; exit 1; }
 export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/train -o train --output-format csv -- python3 tools/prof_train.py > $O/train.log 2>&1 || { tail -5 $O/train.log; exit 1; }
 rm -f $O/train/train_kernel_trace.csv

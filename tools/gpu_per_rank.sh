@@ -7,7 +7,7 @@ O=${1:-gpurun_out/per_rank}; mkdir -p $O; export TMPDIR=/tmp
 for r in $(seq 1 ${REP:-2}); do
 for n in ${NS:-1 2 4 8}; do
   f=$O/per_rank_of_${n}_$r
-  timeout -k 10 600 python3 bench.py --per-rank-of $n --no-cpu-baseline > $f.json 2> $f.err || { tail -20 $f.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --per-rank-of $n --no-cpu-baseline > $f.json 2> $f.err || { tail -20 $f.err; exit 1; }
   python3 -c "
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -52,7 +52,7 @@ if MODE == "dps":
         return ode_func(t1, x0).reshape(shape).to(torch.float32)
     _one_eval.last_nfe = 1
     _cs.get_solver = _one_eval
-common = ["--steps", "1", "--warmup", "1", "--no-roofline", "--no-cpu-baseline", "--ns-steps", "0",
+common = ["--full", "--steps", "1", "--warmup", "1", "--no-roofline", "--no-cpu-baseline", "--ns-steps", "0",
           "--ncddpmpp-steps", "0"]
 argv = {"train": ["--train-steps", "1", "--cifar-steps", "0", "--no-pinn", "--no-dps"],
         "cifar": ["--train-steps", "1", "--train-warmup", "0", "--cifar-steps", "1", "--no-pinn",
