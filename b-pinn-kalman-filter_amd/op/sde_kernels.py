@@ -41,7 +41,7 @@ def predictor(kind, x, model_out, coef, step, *, x_out, x_mean=None, noise=None,
               drift_mul_x=1, seed=0, draw=0, sample_offset=0):
     require_hip(x, model_out, coef, step, what="pc_predictor")
     B = x.shape[0]
-    D = x.numel() // B
+    D = x.numel() // max(B, 1)
     check(lib.bpk_pc_predictor_f32(kind, x.data_ptr(), model_out.data_ptr(), _p(noise),
                                    x_out.data_ptr(), _p(x_mean), B, D, sample_offset,
                                    coef.data_ptr(), _bd(coef, B), step.data_ptr(), score_mode,
@@ -58,7 +58,7 @@ def langevin_norms(model_out, coef, step, workspace, red, *, noise=None, score_m
                    draw=0, sample_offset=0):
     """red[0] = sum_b ||score_b||, red[1] = sum_b ||noise_b|| over the local batch."""
     B = model_out.shape[0]
-    D = model_out.numel() // B
+    D = model_out.numel() // max(B, 1)
     st = stream_ptr(model_out.device)
     check(lib.bpk_langevin_partial_f32(model_out.data_ptr(), _p(noise), workspace.data_ptr(), B, D,
                                        sample_offset, coef.data_ptr(), _bd(coef, B),
@@ -71,7 +71,7 @@ def langevin_norms(model_out, coef, step, workspace, red, *, noise=None, score_m
 def langevin_update(mode, x, model_out, coef, step, red, *, x_out, x_mean=None, noise=None,
                     B_global=None, score_mode=0, snr=0.16, seed=0, draw=0, sample_offset=0):
     B = x.shape[0]
-    D = x.numel() // B
+    D = x.numel() // max(B, 1)
     check(lib.bpk_langevin_update_f32(mode, x.data_ptr(), model_out.data_ptr(), _p(noise),
                                       _p(red), x_out.data_ptr(), _p(x_mean), B, D,
                                       B_global or B, sample_offset, coef.data_ptr(),

@@ -137,7 +137,9 @@ def coef_rows(sde, t, continuous, predictor_kind=None, probability_flow=False):
         if hasattr(sde, "alphas"):
             rows[:, K.C_ALPHA] = sde.alphas.to(t.device)[sde.timestep_index(t)]
         else:
-            rows[:, K.C_ALPHA] = float("nan")  # reference raises (subVPSDE has no alphas)
+            # subVPSDE has no alphas: never read, the correctors refuse sub-VP
+            # (PCEngine.supports, _FusedCorrector.update_fn)
+            rows[:, K.C_ALPHA] = float("nan")
     else:
         rows[:, K.C_ALPHA] = 1.0
     rows[:, K.C_AUX] = sde.marginal_coef(t)[1]
@@ -302,6 +304,9 @@ class _FusedCorrector(Corrector):
     def update_fn(self, x, t, noise_fn=None):
         if not (x.is_cuda and x.dtype == torch.float32):
             return self.torch_update_fn(x, t)
+        if not isinstance(self.sde, sde_lib.VESDE):
+            # sub-VP has no alphas table: AttributeError, as torch_update_fn and the reference
+            getattr(self.sde, "alphas")
         continuous = getattr(self.score_fn, "continuous", True)
         rows = coef_rows(self.sde, t, continuous)[None]
         step = _zero_step(x.device)
@@ -423,6 +428,12 @@ class PCEngine:
     def __init__(self, sde, shape, predictor, corrector, snr, n_steps=1, continuous=False,
                  denoise=True, eps=1e-3, device="cuda", seed=None, use_graph=True, dist_ctx=None,
                  noise_fn=None):
+        if not self.supports(sde, predictor, corrector, False):
+            raise NotImplementedError(
+                f"PCEngine has no fused step for {sde.__class__.__name__} with "
+                f"{getattr(predictor, '__name__', predictor)} / "
+                f"{getattr(corrector, '__name__', corrector)}; get_pc_sampler runs such pairs "
+                "on the reference loop")
         self.sde, self.shape = sde, tuple(shape)
         self.predictor, self.corrector = predictor, corrector
         self.snr, self.n_steps = float(snr), int(n_steps)
@@ -464,9 +475,14 @@ class PCEngine:
     def supports(sde, predictor, corrector, probability_flow):
         if probability_flow or not _fusable_sde(sde):
             return False
-        ok_p = predictor in (EulerMaruyamaPredictor, AncestralSamplingPredictor, NonePredictor) or (
-            predictor is ReverseDiffusionPredictor and isinstance(sde, (sde_lib.VPSDE, sde_lib.VESDE)))
-        ok_c = corrector in (LangevinCorrector, AnnealedLangevinDynamics, NoneCorrector)
+        # sub-VP has no DDPM tables (discrete_betas / alphas): the reference's ancestral
+        # predictor raises NotImplementedError on it and both Langevin correctors
+        # AttributeError; those pairs go to the reference loop, which raises the same
+        tables = isinstance(sde, (sde_lib.VPSDE, sde_lib.VESDE))
+        ok_p = predictor in (EulerMaruyamaPredictor, NonePredictor) or (
+            predictor in (ReverseDiffusionPredictor, AncestralSamplingPredictor) and tables)
+        ok_c = corrector is NoneCorrector or (
+            corrector in (LangevinCorrector, AnnealedLangevinDynamics) and tables)
         return ok_p and ok_c
 
     def _build_tables(self):
@@ -519,6 +535,10 @@ class PCEngine:
             K.predictor(self.pred_kind, x, m, self.coef, self.step, x_out=x, x_mean=x_mean,
                         noise=nz, score_mode=mode, drift_mul_x=int(sde_vp_like), seed=self.seed,
                         draw=0, sample_offset=self.sample_offset)
+        elif self.corr_mode is not None:
+            # NonePredictor returns (x, x): the step's x_mean is the corrector's noisy x, not
+            # its x_mean (reference sampling.py:249-250, :405-406)
+            x_mean.copy_(x)
         K.step_increment(self.step)
 
     def _pc_step(self, model, x, x_mean, i=None):

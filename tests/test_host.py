@@ -95,6 +95,63 @@ def test_engine_supports_reference_pairs():
     assert set(S._PREDICTORS) >= {"euler_maruyama", "reverse_diffusion", "ancestral_sampling",
                                   "none"}
     assert set(S._CORRECTORS) >= {"langevin", "ald", "none"}
+    # sub-VP has no DDPM tables: the pairs the reference raises on are not the engine's
+    sub = S.sde_lib.subVPSDE()
+    assert not S.PCEngine.supports(sub, S.AncestralSamplingPredictor, S.NoneCorrector, False)
+    assert not S.PCEngine.supports(sub, S.EulerMaruyamaPredictor, S.LangevinCorrector, False)
+    assert not S.PCEngine.supports(sub, S.NonePredictor, S.AnnealedLangevinDynamics, False)
+    assert S.PCEngine.supports(sub, S.EulerMaruyamaPredictor, S.NoneCorrector, False)
+
+
+def test_engine_supports_exactly_the_pairs_it_constructs():
+    """Over the 3 SDE x 4 predictor x 3 corrector matrix, supports() is True exactly when the
+    engine constructs (its step tables build), and every table of a supported pair is
+    finite in the columns its kernels read."""
+    import sampling as S
+    import sde_lib
+    from op import sde_kernels as K
+    # N = 25: the smallest round N with beta_max / N < 1 (below it the VP alphas go negative)
+    sdes = [sde_lib.VPSDE(0.1, 20., 25), sde_lib.subVPSDE(0.1, 20., 25),
+            sde_lib.VESDE(0.01, 50., 25)]
+    preds = [S.EulerMaruyamaPredictor, S.ReverseDiffusionPredictor,
+             S.AncestralSamplingPredictor, S.NonePredictor]
+    corrs = [S.LangevinCorrector, S.AnnealedLangevinDynamics, S.NoneCorrector]
+    n_ok = 0
+    for sde in sdes:
+        for p in preds:
+            for c in corrs:
+                what = f"{type(sde).__name__} / {p.__name__} / {c.__name__}"
+                ok = S.PCEngine.supports(sde, p, c, False)
+                assert ok is True or ok is False, what
+                try:
+                    eng = S.PCEngine(sde, (2, 1, 4, 4), p, c, 0.16, 1, continuous=True,
+                                     device="cpu")
+                except (NotImplementedError, AttributeError):
+                    eng = None
+                assert (eng is not None) == ok, what
+                if ok:
+                    n_ok += 1
+                    assert eng.coef.shape == (25, 1, K.COEF_STRIDE)
+                    assert torch.isfinite(eng.coef[..., K.C_SDIV]).all(), what
+                    if c is not S.NoneCorrector:
+                        assert torch.isfinite(eng.coef[..., [K.C_ALPHA, K.C_AUX]]).all(), what
+                    if p is not S.NonePredictor:
+                        assert torch.isfinite(eng.coef[..., K.C_DRIFT:K.C_SQRT_MDT + 1]).all(), what
+    # vp and ve: all 12 pairs; sub-VP: Euler-Maruyama or no predictor, no corrector
+    assert n_ok == 12 + 12 + 2
+
+
+def test_subvp_ancestral_pc_sampler_raises_like_the_reference():
+    import sampling as S
+    import sde_lib
+    sampler = S.get_pc_sampler(sde_lib.subVPSDE(0.1, 20., 12), (2, 1, 4, 4),
+                               S.AncestralSamplingPredictor, S.NoneCorrector, lambda v: v, 0.16,
+                               continuous=True, device="cpu")
+    with pytest.raises(NotImplementedError):
+        sampler(lambda x, t: x)
+    fused = S.LangevinCorrector(sde_lib.subVPSDE(0.1, 20., 12), lambda x, t: x, 0.16, 1)
+    with pytest.raises(AttributeError):
+        fused.update_fn(torch.zeros(2, 1, 4, 4), torch.ones(2) * 0.5)
 
 
 def _gloo_worker(rank, world, port, q):
