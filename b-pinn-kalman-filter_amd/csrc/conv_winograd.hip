@@ -23,7 +23,10 @@
 //     the logical order, which is dealt to one XCD, so they share the input patch in L2.
 // Filter transform U = G g G^T (16 x cin x cout) is a separate, tiny kernel; callers
 // cache U while the weights do not change (sampling).
+// The 16-cin kernel also has an F(2x4, 3x3) form (k16_item24, wino_f24.h): 24 points per 2 x 4
+// tile, 0.75 of the MFMAs for the same conv; the forward convs of the samplers run on it.
 #include "bpk_common.h"
+#include "wino_f24.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -104,6 +107,37 @@ __global__ __launch_bounds__(256) void wino_filter_batch_kernel(const int64_t* _
                     (int)jb[2], (int)jb[3], (int)jb[4], (int)jb[5],
                     (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
                     (int64_t)gridDim.x * blockDim.x);
+}
+
+// U24 = G2 g G4^T of the F(2x4,3x3) form (wino_f24.h: computed in double, rounded once; point
+// order 6 s + j of wino24_slot_row), 24 floats per (cin, cout) laid out per 16-cout group, same
+// CoutP padding rule and ft meaning as wino_filter_range
+__global__ __launch_bounds__(256) void wino_filter24_kernel(const float* __restrict__ w,
+                                                            float* __restrict__ U, int Cin,
+                                                            int Cout, int CoutP, int ft) {
+  const int64_t total = (int64_t)Cin * CoutP;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int co = (int)(i % CoutP);
+    const int ci = (int)(i / CoutP);
+    float u[24];
+    if (co >= Cout) {
+#pragma unroll
+      for (int p = 0; p < 24; ++p) u[p] = 0.f;
+    } else {
+      const float* g = ft ? w + ((int64_t)ci * Cout + co) * 9 : w + ((int64_t)co * Cin + ci) * 9;
+      float gg[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) gg[k] = ft ? g[8 - k] : g[k];
+      wino24_filter(gg, u);
+    }
+    // [cin][cout / 16][q][cout % 16][4]: the 16 couts of a wave's B fragment q are 256
+    // contiguous bytes, so one buffer_load_b128 of the conv kernel reads 4 whole segments
+    f4* dst = reinterpret_cast<f4*>(U) + ((int64_t)ci * (CoutP / 16) + co / 16) * 96 + co % 16;
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+      dst[16 * q] = f4{u[4 * q], u[4 * q + 1], u[4 * q + 2], u[4 * q + 3]};
+  }
 }
 
 struct WinoGeo {
@@ -1164,6 +1198,311 @@ __global__ __launch_bounds__(512, 1) void wino_f23_k16_kernel(
   }
 }
 
+// F(2x4,3x3) form of the 16-cin item (wino_f24.h): the same workgroup, region (8 x 16 pixels),
+// 10 x 18 patch, GroupNorm+SiLU prologue, two-source switch, `up` addressing and split-K slicing
+// as k16_item, but the region is 4 x 4 tiles of 2 rows x 4 columns -- 16 tiles, ONE M block of
+// the 16x16x4 MFMA -- with 24 transform-domain points per tile: 24 points x 4 k-steps = 96 MFMAs
+// per wave and chunk instead of 128 for the same pixels x cin x couts.
+//   * V records: 16 cin x 16 tiles of 24 floats at a 28-float stride (28 i mod 64 over the 16
+//     lanes of a ds_read_b128 group covers the 64 banks once): 2 x 28 KB.  Each thread owns half
+//     a record: wave w transforms half h = w & 1 (slots 2 h, 2 h + 1: the F(2,3) row pass of
+//     patch rows h .. h + 2, then the F(4,3) pass along both rows) of channels 4 kq + (w >> 1),
+//     so a read group's two kq values sit 960 dwords apart (= 0 mod 64 banks).
+//   * accumulators: acc[24] f4 = 96 registers: lane (kq, jj) holds, for cout cout_w + jj, the 24
+//     points of the 4 tiles of tile row kq -- after the output transform 2 rows x 16 contiguous
+//     pixels, 8 f4 strips as k16_item (same stores, skip loads and statistics strips).
+//   * U operands: uo[2][6] f4, one f4 per 4 MFMAs, refilled two k-steps ahead right after use;
+//     U24 is laid out per 16-cout group and fragment so that a wave's load is 4 x 256 B.
+// LDS: 2 x 15 KB patches + 2 x 28 KB V + the GroupNorm table (8 KB) = 94 KB.
+constexpr int kM24 = 16;   // tiles per region
+constexpr int kVS24 = 28;  // LDS stride of one (cin, tile) V record (24 + pad)
+
+template <bool PRE>
+__device__ __forceinline__ void k16_item24(
+    unsigned b, const float* __restrict__ x, const float* __restrict__ U,
+    const float* __restrict__ bias, const float* __restrict__ skip,
+    const float2* __restrict__ pre, float* __restrict__ y, float2* __restrict__ stats,
+    const WinoGeo& g, const float* __restrict__ x2) {
+  constexpr int CK = 16;
+  constexpr int kPatch = CK * kPR * kPCp;
+  __shared__ __attribute__((aligned(16))) float s_patch_raw[2][kPatch];
+  constexpr int kVBuf = CK * kM24 * kVS24;
+  __shared__ __attribute__((aligned(16))) float s_v[2][kVBuf];
+  __shared__ float2 s_ss[PRE ? kPreMaxCin : 1];
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  unsigned cb, rx, ry;
+  unsigned r = udivmod(b, (unsigned)g.cout_blocks, cb);
+  r = udivmod(r, (unsigned)g.regions_x, rx);
+  r = udivmod(r, (unsigned)g.regions_y, ry);
+  unsigned nn;
+  const int ks_idx = (int)udivmod(r, (unsigned)g.N, nn);  // split-K slice (0 unless ksplit > 1)
+  const int n = (int)nn;
+  const int oy0 = (int)ry * kOutRows, ox0 = (int)rx * kOutCols;
+  const int cout_w = (int)cb * 128 + wave * 16;
+  const int ph = __builtin_amdgcn_readfirstlane(tid >> 8);  // channels 8 ph .. 8 ph + 7
+
+  f4 acc[24];
+  const int64_t plane = (int64_t)g.H * g.W;
+  const int up = g.up;
+  const int64_t xplane = plane >> (2 * up);
+  const int C2 = g.Cin - g.C1;
+  const float* xn = x + (int64_t)n * g.C1 * xplane;
+  const float2* pre_n = PRE ? pre + (int64_t)n * g.Cin : nullptr;
+  const int kq = lane >> 4, jj = lane & 15;
+  const int nch = g.Cin / CK / max(g.ksplit, 1);  // chunks of this workgroup
+  const int kb = ks_idx * nch;                    // its first chunk
+
+  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(xn), 0, (int)(g.C1 * xplane * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xrs2 = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(C2 > 0 ? x2 + (int64_t)n * C2 * plane : xn), 0,
+      (int)((C2 > 0 ? C2 : g.C1) * plane * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(U), 0, (int)((int64_t)g.Cin * g.Cout * 96), 0x00020000);
+
+  // 180 patch positions; threads beyond them in a half duplicate position 0 (as k16_item)
+  constexpr int kPos = kPR * kPC;
+  int poff, pdst;
+  bool pin;
+  {
+    const int t8 = tid & 255;
+    const int t = t8 < kPos ? t8 : 0;
+    const int py = t / kPC, px = t - py * kPC;
+    const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
+    pin = iy >= 0 && iy < g.H && ix >= 0 && ix < g.W;
+    const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
+    poff = ((cy >> up) * (g.W >> up) + (cx >> up)) * 4;
+    pdst = py * kPCp + px + ph * 8 * (kPR * kPCp);
+  }
+  float pv[8];
+  auto load_patch_part = [&](float* dst, int k, int c0, int cn) {
+    const int cc = (kb + min(k, nch - 1)) * CK;
+    const bool second = cc >= g.C1;
+    const int soff = ((second ? cc - g.C1 : cc) + ph * 8) * (int)xplane * 4;
+#pragma unroll
+    for (int c = c0; c < c0 + cn; ++c)
+      dst[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+          second ? xrs2 : xrs, poff, soff + c * (int)xplane * 4, 0));
+  };
+  auto store_patch_part = [&](const float* src, float* sp, int k, int c0, int cn) {
+    const int cb0 = (kb + min(k, nch - 1)) * CK + ph * 8;
+#pragma unroll
+    for (int c = c0; c < c0 + cn; ++c) {
+      float v = src[c];
+      if (PRE) {
+        const float2 st = s_ss[cb0 + c];
+        v = silu_f(v * st.x + st.y);
+      }
+      sp[pdst + c * (kPR * kPCp)] = pin ? v : 0.f;
+    }
+  };
+  // B operands: uo[ks & 1][q] = points 4q..4q + 3 of U24 (cin c0 + 4 ks + kq, cout cout_w + jj),
+  // at [cin][cout_w / 16][q][jj] (wino_filter24_kernel): 256 contiguous bytes per kq
+  f4 uo[2][6];
+  const int uoff = ((kq * g.Cout + cout_w) * 24 + jj * 4) * 4;
+  auto u_soff = [&](int k, int ks) {
+    return (((kb + min(k, nch - 1)) * CK + 4 * ks) * g.Cout) * 96;
+  };
+  auto load_u = [&](int slot, int k, int ks) {
+    const int soff = u_soff(k, ks);
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+      uo[slot][q] = __builtin_bit_cast(
+          f4, __builtin_amdgcn_raw_buffer_load_b128(urs, uoff + q * 256, soff, 0));
+  };
+  // V = B2^T d B4: half th of the record (channel tc, tile jj) per thread
+  const int th = __builtin_amdgcn_readfirstlane(wave & 1);
+  const int tc = 4 * kq + (wave >> 1);
+  const int tty = jj >> 2, ttx = jj & 3;
+  float d[3][6];
+  auto read_d = [&](const float* sp) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float* row = &sp[(tc * kPR + 2 * tty + th + i) * kPCp + 4 * ttx];
+      const f4 v4 = *reinterpret_cast<const f4*>(row);
+      const float2 v2 = *reinterpret_cast<const float2*>(row + 4);
+      d[i][0] = v4[0];
+      d[i][1] = v4[1];
+      d[i][2] = v4[2];
+      d[i][3] = v4[3];
+      d[i][4] = v2.x;
+      d[i][5] = v2.y;
+    }
+  };
+  auto write_v = [&](float* sv) {
+    float rx_[6], ry_[6], vx[6], vy[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) wino24_data_rows(d[0][j], d[1][j], d[2][j], th, rx_[j], ry_[j]);
+    wino24_data_cols(rx_, vx);
+    wino24_data_cols(ry_, vy);
+    f4* dst = reinterpret_cast<f4*>(&sv[(tc * kM24 + jj) * kVS24 + 12 * th]);
+    dst[0] = f4{vx[0], vx[1], vx[2], vx[3]};
+    dst[1] = f4{vx[4], vx[5], vy[0], vy[1]};
+    dst[2] = f4{vy[2], vy[3], vy[4], vy[5]};
+  };
+
+  // prologue: V(0) in s_v[0], patch(1) in s_patch[1], patch(2) and U(0) in flight
+  {
+    float pv0[8], pv1[8];
+    load_patch_part(pv0, 0, 0, 8);
+    load_patch_part(pv1, 1, 0, 8);
+    load_patch_part(pv, 2, 0, 8);
+    load_u(0, 0, 0);
+    load_u(1, 0, 1);
+    if (PRE) {
+      for (int c = tid; c < g.Cin; c += 512) s_ss[c] = pre_n[c];
+      __syncthreads();
+    }
+    store_patch_part(pv0, s_patch_raw[0], 0, 0, 8);
+    store_patch_part(pv1, s_patch_raw[1], 1, 0, 8);
+  }
+  __syncthreads();
+  read_d(s_patch_raw[0]);
+  write_v(s_v[0]);
+  __syncthreads();
+
+  // A operands: points 4q..4q + 3 of the record (cin 4 ks + kq, tile jj), in a ring of four
+  // registers quads over the chunk's 24 (ks, q) fragments: fragment i sits in a[i & 3] and is
+  // replaced by fragment i + 4 right after its MFMAs (12 MFMAs before that one is used)
+  f4 a[4];
+  auto a_src = [&](const float* sv, int ks) {
+    return reinterpret_cast<const f4*>(&sv[((4 * ks + kq) * kM24 + jj) * kVS24]);
+  };
+  {
+    const f4* src = a_src(s_v[0], 0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a[q] = src[q];
+  }
+  auto step = [&](int k, auto sb_c, auto first_c) __attribute__((always_inline)) {
+    constexpr int SB = decltype(sb_c)::value;
+    constexpr bool FIRST = decltype(first_c)::value;
+    const float* sv = s_v[SB];
+#pragma unroll
+    for (int grp = 0; grp < 8; ++grp) {  // 12 MFMAs each: k-step grp / 2, points 12 (grp & 1) ..
+      const int ks = grp >> 1, hf = grp & 1;
+      __builtin_amdgcn_sched_barrier(0);
+      if (grp == 0) read_d(s_patch_raw[SB ^ 1]);                        // patch(k+1)
+      if (grp == 1) write_v(s_v[SB ^ 1]);                               // V(k+1)
+      if (grp == 2) store_patch_part(pv, s_patch_raw[SB], k + 2, 0, 4);  // patch(k+2)
+      if (grp == 3) store_patch_part(pv, s_patch_raw[SB], k + 2, 4, 4);
+      if (grp == 4) load_patch_part(pv, k + 3, 0, 4);
+      if (grp == 5) load_patch_part(pv, k + 3, 4, 4);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int qq = 0; qq < 3; ++qq) {
+        const int q = 3 * hf + qq;
+        const int fi = 6 * ks + q;  // fragment index in the chunk
+#pragma unroll
+        for (int pp = 0; pp < 4; ++pp)
+          acc[4 * q + pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+              a[fi & 3][pp], uo[ks & 1][q][pp],
+              (FIRST && ks == 0) ? f4{0.f, 0.f, 0.f, 0.f} : acc[4 * q + pp], 0, 0, 0);
+        if (fi + 4 < 24) a[fi & 3] = a_src(sv, (fi + 4) / 6)[(fi + 4) % 6];
+        // k-step ks + 2 of this chunk, or ks - 2 of the next
+        const int soff = ks < 2 ? u_soff(k, ks + 2) : u_soff(k + 1, ks - 2);
+        uo[ks & 1][q] = __builtin_bit_cast(
+            f4, __builtin_amdgcn_raw_buffer_load_b128(urs, uoff + q * 256, soff, 0));
+      }
+    }
+    __syncthreads();
+    const f4* src = a_src(s_v[SB ^ 1], 0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a[q] = src[q];
+  };
+  using C0 = std::integral_constant<int, 0>;
+  using C1 = std::integral_constant<int, 1>;
+  step(0, C0{}, std::true_type{});
+  int k = 1;
+  for (; k + 1 < nch; k += 2) {
+    step(k, C1{}, std::false_type{});
+    step(k + 1, C0{}, std::false_type{});
+  }
+  if (k < nch) step(k, C1{}, std::false_type{});
+
+  // output transform straight from registers: tile row kq, tiles rg = 0..3 -> output rows
+  // oy0 + 2 kq + h, one f4 strip per tile
+  const float rdiv = 1.f / g.div;
+  if (cout_w < g.CoutS) {
+    const int co = cout_w + jj;
+    const float bv = bias ? bias[co] : 0.f;
+    const int64_t obase = ((int64_t)(ks_idx * g.N + n) * g.CoutS + co) * plane +
+                          (int64_t)(oy0 + 2 * kq) * g.W + ox0;
+    float lm = 0.f, lm2 = 0.f;
+    // residual tail: all eight skip vectors of this lane requested before the first is used
+    f4 skv[2][4];
+    if (skip) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg)
+          skv[h][rg] = *reinterpret_cast<const f4*>(&skip[obase + (int64_t)h * g.W + 4 * rg]);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        float t[6], yv[4];
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+          t[j] = wino24_out_rows(acc[j][rg], acc[6 + j][rg], acc[12 + j][rg], acc[18 + j][rg], h);
+        wino24_out_cols(t, yv);
+        f4 v = f4{yv[0] + bv, yv[1] + bv, yv[2] + bv, yv[3] + bv};
+        const int64_t o = obase + (int64_t)h * g.W + 4 * rg;
+        if (skip) {
+          const f4 sk = skv[h][rg];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) v[c] = div_rn(sk[c] + v[c], g.div, rdiv);
+        }
+        *reinterpret_cast<f4*>(&y[o]) = v;
+        if (stats) {  // strip st = 4 h + rg joins the st strips (4 st values) before it
+          const float sm = ((v[0] + v[1]) + (v[2] + v[3])) * 0.25f;
+          float sm2 = 0.f;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) sm2 = fmaf(v[c] - sm, v[c] - sm, sm2);
+          constexpr float kW[8] = {1.f, 1.f / 2, 1.f / 3, 1.f / 4, 1.f / 5, 1.f / 6, 1.f / 7, 1.f / 8};
+          const int st = 4 * h + rg;
+          const float dd = sm - lm;
+          lm = lm + dd * kW[st];
+          lm2 = (lm2 + sm2) + dd * dd * (4.f * st * kW[st]);
+        }
+      }
+    }
+    if (stats) {
+      merge_stats(lm, lm2, __shfl_xor(lm, 16, 64), __shfl_xor(lm2, 16, 64), 32.f);
+      merge_stats(lm, lm2, __shfl_xor(lm, 32, 64), __shfl_xor(lm2, 32, 64), 64.f);
+      if (kq == 0) {
+        const int R = g.regions_x * g.regions_y;
+        const int region = (oy0 / kOutRows) * g.regions_x + ox0 / kOutCols;
+        stats[((int64_t)n * g.CoutS + co) * R + region] = make_float2(lm, lm2);
+      }
+    }
+  }
+}
+
+// the persistent walk of wino_f23_k16_kernel over F(2x4,3x3) items
+template <bool PRE>
+__global__ __launch_bounds__(512, 1) void wino_f24_k16_kernel(
+    const float* __restrict__ x, const float* __restrict__ U, const float* __restrict__ bias,
+    const float* __restrict__ skip, const float2* __restrict__ pre, float* __restrict__ y,
+    float2* __restrict__ stats, WinoGeo g, int xcd_remap, const float* __restrict__ x2,
+    unsigned items) {
+  const unsigned G = gridDim.x, w = blockIdx.x;
+  unsigned first = w, stride = G, end = items;
+  if (xcd_remap) {  // G % 8 == 0: XCD label w % 8 owns items [start, start + count)
+    const unsigned xc = w & 7u, q = items >> 3, r = items & 7u;
+    const unsigned start = xc * q + min(xc, r);
+    first = start + (w >> 3);
+    stride = G >> 3;
+    end = start + q + (xc < r ? 1u : 0u);
+  }
+  for (unsigned b = first; b < end; b += stride) {
+    if (b != first) __syncthreads();
+    k16_item24<PRE>(b, x, U, bias, skip, pre, y, stats, g, x2);
+  }
+}
+
 // Split-K epilogue: y = sum_s part[s] + bias, or (skip + that) / div, and the GroupNorm partial
 // statistics of the stored values, as the 16-cin kernel's own epilogue (the partial slabs are
 // summed in a fixed order: deterministic).  One workgroup = 8 channels x one 8 x 16 region of
@@ -1514,6 +1853,107 @@ extern "C" int bpk_conv3x3_wino_up2_f32(const float* x, const float* U, const fl
                      (kg % 8 == 0) ? 1 : 0, nullptr, (unsigned)items);
   BPK_LAUNCH_CHECK("conv3x3_wino_up2");
   return BPK_OK;
+}
+
+// ---- F(2x4,3x3) form of the 16-cin kernel (k16_item24): its own filter layout U24 ----------
+// WINO_NO_F24 builds (A/B) report the form unsupported, so every caller stays on F(2x2).
+
+extern "C" int bpk_conv3x3_wino_f24_supported(int N, int Cin, int C1, int Cout, int H, int W) {
+#ifdef WINO_NO_F24
+  return 0;
+#else
+  return N > 0 && Cin > 0 && Cin % 16 == 0 && Cin <= kPreMaxCin && C1 > 0 && C1 <= Cin &&
+         C1 % 16 == 0 && Cout > 0 && Cout % 16 == 0 && cout_padded(Cout) % 128 == 0 && H > 0 &&
+         H % kOutRows == 0 && W > 0 && W % kOutCols == 0;
+#endif
+}
+
+extern "C" int64_t bpk_conv3x3_wino_filter24_bytes(int Cin, int Cout) {
+  return (int64_t)24 * Cin * cout_padded(Cout) * (int64_t)sizeof(float);
+}
+
+static int wino_filter24(const float* weight, float* U, int Cin, int Cout, int ft, void* stream) {
+  BPK_REQUIRE(Cin > 0 && Cout > 0, "conv3x3_wino_filter24: bad channels %d -> %d", Cin, Cout);
+  const int64_t total = (int64_t)Cin * cout_padded(Cout);
+  hipLaunchKernelGGL(wino_filter24_kernel,
+                     dim3((unsigned)std::min<int64_t>(bpk::ceil_div(total, 256), 4096)), dim3(256),
+                     0, bpk::as_stream(stream), weight, U, Cin, Cout, cout_padded(Cout), ft);
+  BPK_LAUNCH_CHECK("conv3x3_wino_filter24");
+  return BPK_OK;
+}
+
+extern "C" int bpk_conv3x3_wino_filter24_f32(const float* weight, float* U, int Cin, int Cout,
+                                             void* stream) {
+  return wino_filter24(weight, U, Cin, Cout, 0, stream);
+}
+
+extern "C" int bpk_conv3x3_wino_filter24_ft_f32(const float* weight, float* U, int Cin, int Cout,
+                                                void* stream) {
+  return wino_filter24(weight, U, Cin, Cout, 1, stream);
+}
+
+// one launch of wino_f24_k16_kernel: S > 1 writes raw partial slabs to y (no epilogue)
+static int wino_f24_launch(const float* x, const float* x2, int C1, const float* pre,
+                           const float* U, const float* bias, const float* skip, float div,
+                           float* y, float* stats, int N, int Cin, int Cout, int H, int W, int up,
+                           int S, WinoGeo* geo, void* stream) {
+  BPK_REQUIRE(bpk_conv3x3_wino_f24_supported(N, Cin, C1, Cout, H, W),
+              "conv3x3_wino_f24: unsupported shape N=%d Cin=%d (C1=%d) Cout=%d H=%d W=%d (need "
+              "Cin, C1 %% 16, Cout %% 128, H %% 8, W %% 16 == 0, Cin <= %d)", N, Cin, C1, Cout, H,
+              W, kPreMaxCin);
+  const int CoutP = cout_padded(Cout);
+  WinoGeo gk{N, Cin, CoutP, H, W, W / kOutCols, H / kOutRows, CoutP / 128, div, C1, Cout, up, S};
+  const int64_t items = (int64_t)N * gk.regions_x * gk.regions_y * gk.cout_blocks * S;
+  BPK_REQUIRE(items < (1LL << 31), "conv3x3_wino_f24: grid too large");
+  const float2* kpre = reinterpret_cast<const float2*>(pre);
+  float2* stats2 = reinterpret_cast<float2*>(stats);
+  hipStream_t st = bpk::as_stream(stream);
+  const unsigned kg = k16_grid(items);
+  const int remap = (kg % 8 == 0) ? 1 : 0;
+  if (pre)
+    hipLaunchKernelGGL((wino_f24_k16_kernel<true>), dim3(kg), dim3(512), 0, st, x, U, bias, skip,
+                       kpre, y, stats2, gk, remap, x2, (unsigned)items);
+  else
+    hipLaunchKernelGGL((wino_f24_k16_kernel<false>), dim3(kg), dim3(512), 0, st, x, U, bias, skip,
+                       kpre, y, stats2, gk, remap, x2, (unsigned)items);
+  BPK_LAUNCH_CHECK("conv3x3_wino_f24");
+  if (geo) *geo = gk;
+  return BPK_OK;
+}
+
+// bpk_conv3x3_wino_splitk_f32 with a U24 filter (bpk_conv3x3_wino_filter24_f32): same split
+// rule, workspace (bpk_conv3x3_wino_splitk_bytes) and reduce kernel -- the partial slabs are in
+// the output domain
+extern "C" int bpk_conv3x3_wino_f24_splitk_f32(const float* x, const float* x2, int C1,
+                                               const float* pre, const float* U,
+                                               const float* bias, const float* skip, float div,
+                                               float* y, float* stats, float* workspace, int N,
+                                               int Cin, int Cout, int H, int W, void* stream) {
+  if (!x2) C1 = Cin;
+  const int S = wino_splits(N, Cin, C1, Cout, H, W);
+  if (S <= 1)
+    return wino_f24_launch(x, x2, C1, pre, U, bias, skip, div, y, stats, N, Cin, Cout, H, W, 0, 1,
+                           nullptr, stream);
+  BPK_REQUIRE(workspace != nullptr, "conv3x3_wino_f24_splitk: workspace is NULL");
+  WinoGeo gk;
+  const int rc = wino_f24_launch(x, x2, C1, pre, U, nullptr, nullptr, div, workspace, nullptr, N,
+                                 Cin, Cout, H, W, 0, S, &gk, stream);
+  if (rc != BPK_OK) return rc;
+  const int64_t rblocks = (int64_t)N * (Cout / 8) * gk.regions_x * gk.regions_y;
+  BPK_REQUIRE(rblocks < (1LL << 31), "conv3x3_wino_f24_splitk: reduce grid");
+  hipLaunchKernelGGL(wino_splitk_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0,
+                     bpk::as_stream(stream), workspace, S, bias, skip, y,
+                     reinterpret_cast<float2*>(stats), gk);
+  BPK_LAUNCH_CHECK("conv3x3_wino_f24_splitk_reduce");
+  return BPK_OK;
+}
+
+// bpk_conv3x3_wino_up2_f32 with a U24 filter
+extern "C" int bpk_conv3x3_wino_f24_up2_f32(const float* x, const float* U, const float* bias,
+                                            float* y, int N, int Cin, int Cout, int H, int W,
+                                            void* stream) {
+  return wino_f24_launch(x, nullptr, Cin, nullptr, U, bias, nullptr, 1.0f, y, nullptr, N, Cin,
+                         Cout, H, W, 1, 1, nullptr, stream);
 }
 
 extern "C" int bpk_conv3x3_wino_pre_f32(const float* x, const float* pre, const float* U,

@@ -1,5 +1,6 @@
-"""3x3 convolution on the fused Winograd F(2x2,3x3) MFMA kernel (csrc/conv_winograd.hip), or
-on the small-channel VALU kernel (csrc/conv_small.hip) when Cin <= 4 or Cout <= 4.
+"""3x3 convolution on the fused Winograd MFMA kernels (csrc/conv_winograd.hip: F(2x2,3x3), and
+its F(2x4,3x3) form with 0.75 of the MFMAs for the forward convs the 16-cin kernel takes, see
+`wino_form`), or on the small-channel VALU kernel (csrc/conv_small.hip) when Cin <= 4 or Cout <= 4.
 
 `conv3x3(x, weight, bias=None)` == F.conv2d(x, weight, bias, stride=1, padding=1) for
 fp32 NCHW HIP tensors whose shape the kernel supports (`supported(...)`).  Backward: the
@@ -78,19 +79,25 @@ def static_filters(registry: list):
         _STATIC_FILTERS = prev
 
 
-def _transform_into(weight, U, ft):
+def _filter_fn(ft, form):
+    if form == 24:
+        return lib.bpk_conv3x3_wino_filter24_ft_f32 if ft else lib.bpk_conv3x3_wino_filter24_f32
+    return lib.bpk_conv3x3_wino_filter_ft_f32 if ft else lib.bpk_conv3x3_wino_filter_f32
+
+
+def _transform_into(weight, U, ft, form=16):
     w = weight.detach().contiguous()
     Cout, Cin = (w.shape[1], w.shape[0]) if ft else (w.shape[0], w.shape[1])
-    fn = lib.bpk_conv3x3_wino_filter_ft_f32 if ft else lib.bpk_conv3x3_wino_filter_f32
-    check(fn(w.data_ptr(), U.data_ptr(), Cin, Cout, stream_ptr(w.device)), "conv3x3 filter")
+    check(_filter_fn(ft, form)(w.data_ptr(), U.data_ptr(), Cin, Cout, stream_ptr(w.device)),
+          "conv3x3 filter")
 
 
 def refresh_filters(registry: list):
     """Recompute, in place, the registered transforms whose weight changed since capture."""
-    for i, (weight, U, ft, ver) in enumerate(registry):
+    for i, (weight, U, ft, ver, form) in enumerate(registry):
         if weight._version != ver:
-            _transform_into(weight, U, ft)
-            registry[i] = (weight, U, ft, weight._version)
+            _transform_into(weight, U, ft, form)
+            registry[i] = (weight, U, ft, weight._version, form)
 
 
 _FILTER_BATCH = None  # {(weight data_ptr, ft): (shape, U)} while a FilterBatch is active
@@ -177,17 +184,36 @@ def batched_filters(module, enabled=True):
         yield fb
 
 
-def filter_transform(weight, ft=False):
-    """U [Cin, CoutP, 16] (CoutP = Cout rounded up to 64), cached on `weight` while its
-    version counter is unchanged.  ft=True: the transform of _flip_t(weight) (the filter of
-    the backward-data conv, Cin = weight.shape[0]), read from `weight` in place.  Inside an
-    active FilterBatch: its static buffer."""
+# BPK_WINO_F24=0: every conv stays on the F(2x2,3x3) form (16 points); read once at import
+_F24 = os.environ.get("BPK_WINO_F24", "1") != "0"
+last_form = None  # points per tile (16 or 24) of the most recent Winograd forward launch
+
+
+def wino_form(weight, ft, N, C, C1, Cout, H, W):
+    """24 = the F(2x4,3x3) form of the 16-cin kernel (0.75 of the MFMAs), when the shape has it
+    (bpk_conv3x3_wino_f24_supported), the filter is not flipped (backward-data stays on 16
+    points), no FilterBatch is active (it holds 16-point buffers: the training steps) and
+    BPK_WINO_F24 is not 0; else 16."""
+    if not _F24 or ft or _FILTER_BATCH is not None:
+        return 16
+    return 24 if lib.bpk_conv3x3_wino_f24_supported(N, C, C1, Cout, H, W) else 16
+
+
+def filter_transform(weight, ft=False, form=16):
+    """The filter transform U of `weight`, Cin x CoutP x form floats (CoutP = Cout rounded up to
+    64; form = 16: F(2x2,3x3) as [Cin, CoutP, 16]; form = 24: F(2x4,3x3) in the layout of
+    bpk_conv3x3_wino_filter24_f32), cached on `weight` per form while its version counter is
+    unchanged.  ft=True: the transform of _flip_t(weight) (the filter of the backward-data
+    conv, Cin = weight.shape[0]), read from `weight` in place.  Inside an active FilterBatch
+    (16-point buffers only): its static buffer."""
+    if form not in (16, 24):
+        raise ValueError(f"filter_transform: form {form} (16 or 24)")
     fbm = _FILTER_BATCH
-    if fbm is not None and weight.is_contiguous():
+    if fbm is not None and form == 16 and weight.is_contiguous():
         e = fbm.get((weight.data_ptr(), bool(ft)))
         if e is not None and e[0] == tuple(weight.shape):
             return e[1]
-    attr = "_bpk_wino_u_ft" if ft else "_bpk_wino_u"
+    attr = ("_bpk_wino_u_ft" if ft else "_bpk_wino_u") + ("24" if form == 24 else "")
     # under hipGraph capture the transform is recorded (and the cache left alone): replays
     # run after optimizer steps have rewritten the weight in place, so a cached U baked into
     # the graph would be stale from the second replay on -- unless the capture registers it
@@ -197,7 +223,7 @@ def filter_transform(weight, ft=False):
     if capturing and _STATIC_FILTERS is not None and cached is not None \
             and cached[0] == weight._version:
         if not any(e[1] is cached[1] for e in _STATIC_FILTERS):
-            _STATIC_FILTERS.append((weight, cached[1], ft, weight._version))
+            _STATIC_FILTERS.append((weight, cached[1], ft, weight._version, form))
         return cached[1]
     if capturing:
         cached = None
@@ -207,9 +233,9 @@ def filter_transform(weight, ft=False):
     Cout, Cin = (w.shape[1], w.shape[0]) if ft else (w.shape[0], w.shape[1])
     # Cout % 64 != 0: U is laid out for Cout rounded up to 64 (zero couts, never stored)
     CoutP = lib.bpk_conv3x3_wino_filter_bytes(Cin, Cout) // (16 * 4 * Cin)
-    U = torch.empty((Cin, CoutP, 16), dtype=torch.float32, device=w.device)
-    fn = lib.bpk_conv3x3_wino_filter_ft_f32 if ft else lib.bpk_conv3x3_wino_filter_f32
-    check(fn(w.data_ptr(), U.data_ptr(), Cin, Cout, stream_ptr(w.device)), "conv3x3 filter")
+    U = torch.empty((Cin, CoutP, form), dtype=torch.float32, device=w.device)
+    check(_filter_fn(ft, form)(w.data_ptr(), U.data_ptr(), Cin, Cout, stream_ptr(w.device)),
+          "conv3x3 filter")
     if not capturing:
         setattr(weight, attr, (weight._version, U))
     return U
@@ -265,7 +291,9 @@ def conv3x3_fwd_raw(x, weight, bias=None, skip=None, div=1.0, pre=None, stats=Fa
         if x2.shape[0] != N or tuple(x2.shape[2:]) != (H, W) or C1 % 8:
             raise RuntimeError(f"conv3x3: second source {tuple(x2.shape)} vs {tuple(x.shape)}")
     Cout = weight.shape[1] if ft else weight.shape[0]
-    U = filter_transform(weight, ft)
+    global last_form
+    form = last_form = wino_form(weight, ft, N, C, C1, Cout, H, W)
+    U = filter_transform(weight, ft, form)
     y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
     b = None if bias is None else bias.detach().contiguous()
     sk = None if skip is None else skip.detach().contiguous()
@@ -283,14 +311,16 @@ def conv3x3_fwd_raw(x, weight, bias=None, skip=None, div=1.0, pre=None, stats=Fa
     # allocator (the graph's pool under capture)
     nws = lib.bpk_conv3x3_wino_splitk_bytes(N, C, C1 if x2 is not None else C, Cout, H, W)
     ws = torch.empty(nws // 4, dtype=torch.float32, device=x.device) if nws > 0 else None
-    check(lib.bpk_conv3x3_wino_splitk_f32(
+    fn = lib.bpk_conv3x3_wino_f24_splitk_f32 if form == 24 else lib.bpk_conv3x3_wino_splitk_f32
+    check(fn(
         x.data_ptr(), None if x2 is None else x2.data_ptr(), C1,
         None if pr is None else pr.data_ptr(), U.data_ptr(),
         None if b is None else b.data_ptr(), None if sk is None else sk.data_ptr(), float(div),
         y.data_ptr(), None if part is None else part.data_ptr(),
         None if ws is None else ws.data_ptr(), N, C, Cout, H, W,
         stream_ptr(x.device)), "conv3x3_wino")
-    flops.wino3x3("wino_dgrad" if ft else "wino_fwd", N, C, Cout, H, W)
+    flops.wino3x3("wino_dgrad" if ft else "wino_fwd24" if form == 24 else "wino_fwd",
+                  N, C, Cout, H, W, form)
     if part is not None:
         attach_gn_partials(y, part, R)
     return y
@@ -1266,14 +1296,15 @@ def _up2_raw(x, weight, bias):
     x = x.detach().contiguous()
     N, C, H, W = x.shape
     Cout = weight.shape[0]
-    U = filter_transform(weight, False)
+    global last_form
+    form = last_form = wino_form(weight, False, N, C, C, Cout, 2 * H, 2 * W)
+    U = filter_transform(weight, False, form)
     y = torch.empty((N, Cout, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
     b = None if bias is None else bias.detach().contiguous()
-    check(lib.bpk_conv3x3_wino_up2_f32(x.data_ptr(), U.data_ptr(),
-                                       None if b is None else b.data_ptr(), y.data_ptr(),
-                                       N, C, Cout, 2 * H, 2 * W, stream_ptr(x.device)),
-          "conv3x3_wino_up2")
-    flops.wino3x3("wino_fwd", N, C, Cout, 2 * H, 2 * W)
+    fn = lib.bpk_conv3x3_wino_f24_up2_f32 if form == 24 else lib.bpk_conv3x3_wino_up2_f32
+    check(fn(x.data_ptr(), U.data_ptr(), None if b is None else b.data_ptr(), y.data_ptr(),
+             N, C, Cout, 2 * H, 2 * W, stream_ptr(x.device)), "conv3x3_wino_up2")
+    flops.wino3x3("wino_fwd24" if form == 24 else "wino_fwd", N, C, Cout, 2 * H, 2 * W, form)
     return y
 
 

@@ -8,7 +8,8 @@ TorchDispatchMode over torch.utils.flop_counter's per-op formulas (FlopCounterMo
 adds module-tracking autograd hooks that cannot run inside the PINN residual's
 torch.autograd.grad passes).  Two bases per launch:
   executed  the multiplies the kernel actually issues -- Winograd F(2x2,3x3) does 16 per
-            2x2 output tile per (cin, cout), i.e. 4/9 of the direct count;
+            2x2 output tile per (cin, cout), i.e. 4/9 of the direct count, its F(2x4,3x3)
+            form (kind wino_fwd24) 24 per 2x4 tile, 1/3 of it;
   direct    2 * MACs of the direct convolution / GEMM (SURVEY.md 8(d)'s FlopCounterMode basis).
 aten ops are counted on the direct basis in both (what MIOpen executes is not visible).
 Outside a `counting()` block `add` is one list check.
@@ -54,10 +55,15 @@ def add(kind, executed, direct=None):
             t.add(kind, float(executed), float(executed if direct is None else direct))
 
 
-def wino3x3(kind, N, C, Cout, H, W):
-    """Winograd F(2x2,3x3): 16 multiplies per 2x2 tile per (cin, cout) vs 9 per pixel."""
+def wino3x3(kind, N, C, Cout, H, W, form=16):
+    """Winograd F(2x2,3x3): 16 multiplies per 2x2 tile per (cin, cout) vs 9 per pixel; form=24,
+    F(2x4,3x3): 24 per 2x4 tile, i.e. 6 N C Cout H W FLOP."""
     if _ACTIVE:
-        add(kind, 32.0 * N * C * Cout * ((H + 1) // 2) * ((W + 1) // 2), 18.0 * N * C * Cout * H * W)
+        if form == 24:
+            executed = 48.0 * N * C * Cout * ((H + 1) // 2) * ((W + 3) // 4)
+        else:
+            executed = 32.0 * N * C * Cout * ((H + 1) // 2) * ((W + 1) // 2)
+        add(kind, executed, 18.0 * N * C * Cout * H * W)
 
 
 def _aten_mode():

@@ -476,6 +476,31 @@ int bpk_conv3x3_wino_splitk_f32(const float* x, const float* x2, int C1, const f
 int bpk_conv3x3_wino_up2_supported(int N, int Cin, int Cout, int H, int W);
 int bpk_conv3x3_wino_up2_f32(const float* x, const float* U, const float* bias, float* y, int N,
                              int Cin, int Cout, int H, int W, void* stream);
+/* Winograd F(2x4,3x3) form of the 16-cin kernel (F(2,3) down the rows, F(4,3) along the row,
+ * points 0, 1, -1, 1/2, -2, inf; csrc/wino_f24.h): 24 transform-domain products per 2 x 4 output
+ * tile instead of 32 -- 0.75 of the MFMAs of the F(2x2) form for the same conv, at about 2.4 x its
+ * fp32 rounding error (still ~1e-6 of max|y|).
+ *   supported(): Cin % 16, C1 % 16, Cout % 16 == 0 with Cout rounded up to 64 a multiple of 128,
+ *                H % 8, W % 16 == 0, Cin <= 1024 (C1 = Cin without a second source)
+ *   filter: U24 = G2 w G4^T computed in double and rounded once: 24 floats per (cin, cout) in the
+ *           kernel's own point order, grouped [Cin][CoutP / 16][6][16][4] so that a wave's
+ *           operand load is contiguous (with the 96-byte-per-cout layout the conv was L2-fetch
+ *           bound and slower than F(2x2)); an opaque blob that only filter24_f32 / _ft_f32
+ *           write.  filter24_bytes() sizes it, _ft_ as bpk_conv3x3_wino_filter_ft_f32
+ *   f24_splitk_f32 / f24_up2_f32: the contracts of bpk_conv3x3_wino_splitk_f32 (same
+ *           bpk_conv3x3_wino_splitk_bytes workspace, may be NULL when that is 0) and
+ *           bpk_conv3x3_wino_up2_f32, with a U24 filter. */
+int bpk_conv3x3_wino_f24_supported(int N, int Cin, int C1, int Cout, int H, int W);
+int64_t bpk_conv3x3_wino_filter24_bytes(int Cin, int Cout);
+int bpk_conv3x3_wino_filter24_f32(const float* weight, float* U, int Cin, int Cout, void* stream);
+int bpk_conv3x3_wino_filter24_ft_f32(const float* weight, float* U, int Cin, int Cout,
+                                     void* stream);
+int bpk_conv3x3_wino_f24_splitk_f32(const float* x, const float* x2, int C1, const float* pre,
+                                    const float* U, const float* bias, const float* skip,
+                                    float div, float* y, float* stats, float* workspace, int N,
+                                    int Cin, int Cout, int H, int W, void* stream);
+int bpk_conv3x3_wino_f24_up2_f32(const float* x, const float* U, const float* bias, float* y, int N,
+                                 int Cin, int Cout, int H, int W, void* stream);
 /* Weight gradient of the same conv (the backward-filter convolution cuDNN / MIOpen runs
  * for nn.Conv2d's autograd): dw [Cout, Cin, 3, 3] = d(sum y * gy)/dw for x [N, Cin, H, W],
  * gy [N, Cout, H, W].  Winograd F(2x2,3x3): per transform position a split-K GEMM
