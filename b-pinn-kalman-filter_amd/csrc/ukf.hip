@@ -1,0 +1,390 @@
+// Square-root unscented Kalman filter (Van der Merwe & Wan 2001, Merwe scaled sigma points),
+// batched over N independent filters of state dimension n <= 64 and observation dimension
+// <= 64, float32 (include/bpk.h, section "ukf").  One 256-thread block per filter:
+//
+//   k_sigma   S staged in LDS (stride 65), 2n+1 point rows written coalesced on n.
+//   k_root    the (2n + d) x d matrix [sqrt(wi) D_1..D_2n ; R^T] lives in LDS (192 x 65 floats
+//             = 48.75 KB at n = d = 64); Householder QR in place, d reflections, all four waves
+//             (wave w owns rows k + w, k + w + 4, ...; lane = column); then wave 0 takes one row
+//             of S = R^T per lane into registers for the sign fix and the point-0 rank-1
+//             up/downdate.
+//   k_update  P_xz by an LDS-tiled fma loop (chunks of 32 sigma points, 4 x 4 outputs per
+//             thread), then wave 0 alone, lane = row: U = P_xz S_z^-T by forward substitution,
+//             y = S_z^-1 (z - zhat), m+ = m- + U y (= m- + K (z - zhat), K = U S_z^-1), and the
+//             obs-dim rank-1 downdates of S- by the columns of U (= K S_z) with the row of S in
+//             64 registers and S_kk / x_k broadcast by v_readlane: no barrier and no LDS access
+//             inside the n x obs-dim chain.
+//
+// LDS tiles are [64][65]: a column walk (lane = row, fixed column) and a row walk (lane =
+// column) both touch 32 distinct banks per half wave (65 mod 32 = 1).
+//
+// Point rows are ordered (g, s, r): filter i = g * (N / groups) + r has its sigma point s at row
+// (g * (2n + 1) + s) * (N / groups) + r.
+//
+// Loss of positive definiteness in a downdate (S_kk^2 - x_k^2 <= 0, or NaN) is a numerical
+// condition, not an error: S_kk := eps_f32 |S_kk|, the rest of that vector is dropped (so
+// nothing can grow without bound), and the filter's status is set to 1.  All loops have trip
+// counts fixed by (n, d); no atomics; every reduction has a fixed order.
+#include "bpk_common.h"
+
+#include <cfloat>
+#include <cmath>
+
+// no implicit FMA contraction: the sigma points must round like torch's separate gamma * S and
+// m +- (.) float32 ops (bit-exact test); every fused multiply-add below is an explicit fmaf
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kMaxDim = 64;
+constexpr int kLd = 65;  // LDS row stride of a 64-wide tile
+constexpr int kThreads = 256;
+constexpr int kWaves = 4;
+
+struct Rows {  // (g, s, r) row addressing of one filter
+  int64_t base, stride;
+  __device__ Rows(int64_t filter, int64_t N, int groups, int n) {
+    const int64_t ng = N / groups, g = filter / ng, r = filter % ng;
+    base = g * (2 * n + 1) * ng + r;
+    stride = ng;
+  }
+  __device__ int64_t row(int s) const { return base + s * stride; }
+};
+
+__device__ __forceinline__ float lane_bcast(float v, int k) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// Rank-1 update (SIGN = +1) / downdate (SIGN = -1) of a lower Cholesky factor held one row per
+// lane (row[k] = S[lane][k]; lanes >= n and the upper triangle hold zeros and stay zero) by the
+// vector x (one element per lane).  One wave, no memory access.
+template <int SIGN>
+__device__ __forceinline__ void chol_rank1(float (&row)[kMaxDim], float x, int n, int lane,
+                                           int& flag) {
+#pragma unroll
+  for (int k = 0; k < kMaxDim; ++k) {
+    if (k < n) {  // wave-uniform
+      const float skk = lane_bcast(row[k], k);
+      const float xk = lane_bcast(x, k);
+      const float r2 = fmaf((float)SIGN * xk, xk, skk * skk);
+      if (SIGN < 0 && !(r2 > 0.f)) {  // wave-uniform: not positive definite (or NaN)
+        flag = 1;
+        if (lane == k) row[k] = FLT_EPSILON * fabsf(skk);
+        x = 0.f;
+      } else {
+        const float r = sqrtf(r2);
+        const float rinv = 1.f / r, sinv = 1.f / skk;
+        // (S + sign s x) / c = (S S_kk + sign x_k x) / r;  c x - s S' = (r x - x_k S') / S_kk
+        const float snew = fmaf((float)SIGN * xk, x, row[k] * skk) * rinv;
+        if (lane > k) {
+          row[k] = snew;
+          x = fmaf(r, x, -xk * snew) * sinv;
+        } else if (lane == k) {
+          row[k] = r;
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void k_sigma(const float* __restrict__ mean,
+                                                    const float* __restrict__ S,
+                                                    float* __restrict__ out, int64_t N, int n,
+                                                    float gamma, int groups) {
+  __shared__ float St[kMaxDim * kLd];
+  const int64_t f = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float* Sf = S + f * n * n;
+  for (int idx = tid; idx < n * n; idx += kThreads) St[(idx / n) * kLd + idx % n] = Sf[idx];
+  __syncthreads();
+  if (lane >= n) return;
+  const Rows rows(f, N, groups, n);
+  const float m = mean[f * n + lane];
+  for (int s = w; s < 2 * n + 1; s += kWaves) {
+    float v = m;  // two roundings, as m + gamma * S evaluated op by op
+    if (s >= 1 && s <= n) v = m + gamma * St[lane * kLd + s - 1];
+    if (s > n) v = m - gamma * St[lane * kLd + s - 1 - n];
+    out[rows.row(s) * n + lane] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void k_root(const float* __restrict__ pts,
+                                                   const float* __restrict__ noise,
+                                                   float* __restrict__ mean_out,
+                                                   float* __restrict__ tril_out,
+                                                   int* __restrict__ status, int64_t N, int n,
+                                                   int d, float wm0, float wc0, float wi,
+                                                   int groups) {
+  __shared__ float A[3 * kMaxDim * kLd];  // rows 0..2n-1: deviations, 2n..2n+d-1: R^T
+  __shared__ float part[kWaves * kMaxDim];
+  __shared__ float red[kWaves];
+  const int64_t f = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const Rows rows(f, N, groups, n);
+  const int ns = 2 * n, M = ns + d;
+
+  for (int t = w; t < ns; t += kWaves)
+    A[t * kLd + lane] = lane < d ? pts[rows.row(t + 1) * d + lane] : 0.f;
+  const float y0 = lane < d ? pts[rows.row(0) * d + lane] : 0.f;
+  {  // R^T below the deviations: lane = column k of the factor, lower triangle only
+    const float* Rf = noise + f * d * d;
+    for (int j = w; j < d; j += kWaves)
+      if (lane < d) A[(ns + lane) * kLd + j] = lane <= j ? Rf[j * d + lane] : 0.f;
+  }
+  __syncthreads();
+
+  // weighted mean: four partial sums per column, fixed order
+  float acc = 0.f;
+  for (int t = w; t < ns; t += kWaves) acc += A[t * kLd + lane];
+  part[w * kMaxDim + lane] = acc;
+  __syncthreads();
+  const float ybar =
+      fmaf(wm0, y0, wi * ((part[lane] + part[kMaxDim + lane]) +
+                          (part[2 * kMaxDim + lane] + part[3 * kMaxDim + lane])));
+  const float swi = sqrtf(wi);
+  for (int t = w; t < ns; t += kWaves) A[t * kLd + lane] = swi * (A[t * kLd + lane] - ybar);
+  const float x0 = lane < d ? sqrtf(fabsf(wc0)) * (y0 - ybar) : 0.f;
+  if (w == 0 && lane < d) mean_out[f * d + lane] = ybar;
+  __syncthreads();
+
+  // Householder QR, R only: after step k row k of A holds R[k][k..d-1]
+  for (int k = 0; k < d; ++k) {
+    const int i0 = k + tid;
+    const float cv = i0 < M ? A[i0 * kLd + k] : 0.f;
+    const float ws = wave_sum(cv * cv);
+    if (lane == 0) red[w] = ws;
+    const float akk = A[k * kLd + k];
+    __syncthreads();
+    const float sigma = (red[0] + red[1]) + (red[2] + red[3]);
+    const float nrm = sqrtf(sigma);
+    const float alpha = akk >= 0.f ? -nrm : nrm;
+    const float vk = akk - alpha;
+    const float beta = sigma > 0.f ? 1.f / (nrm * (nrm + fabsf(akk))) : 0.f;
+    const bool col = lane > k && lane < d;
+    float dot = 0.f;
+    if (col) {
+      for (int i = k + w; i < M; i += kWaves) {
+        const float vi = i == k ? vk : A[i * kLd + k];
+        dot = fmaf(vi, A[i * kLd + lane], dot);
+      }
+    }
+    part[w * kMaxDim + lane] = dot;
+    __syncthreads();
+    if (col) {
+      const float wj = beta * ((part[lane] + part[kMaxDim + lane]) +
+                               (part[2 * kMaxDim + lane] + part[3 * kMaxDim + lane]));
+      for (int i = k + w; i < M; i += kWaves) {
+        const float vi = i == k ? vk : A[i * kLd + k];
+        A[i * kLd + lane] = fmaf(-vi, wj, A[i * kLd + lane]);
+      }
+    }
+    if (w == 0 && lane == k) A[k * kLd + k] = alpha;
+    __syncthreads();
+  }
+
+  // wave 0: S = R^T with a positive diagonal, one row per lane, then the point-0 term
+  float* St = A + kMaxDim * kLd;  // rows 64..127 of A: output staging, disjoint from R
+  if (w == 0) {
+    float row[kMaxDim];
+#pragma unroll
+    for (int k = 0; k < kMaxDim; ++k) {
+      row[k] = 0.f;
+      if (k < d) {
+        const float sg = A[k * kLd + k] < 0.f ? -1.f : 1.f;
+        if (lane < d && k <= lane) row[k] = sg * A[k * kLd + lane];
+      }
+    }
+    int flag = 0;
+    if (wc0 > 0.f) chol_rank1<1>(row, x0, d, lane, flag);
+    if (wc0 < 0.f) chol_rank1<-1>(row, x0, d, lane, flag);
+#pragma unroll
+    for (int k = 0; k < kMaxDim; ++k) St[lane * kLd + k] = row[k];
+    if (lane == 0) status[f] = flag;
+  }
+  __syncthreads();
+  float* So = tril_out + f * d * d;
+  for (int idx = tid; idx < d * d; idx += kThreads) So[idx] = St[(idx / d) * kLd + idx % d];
+}
+
+// ---------------------------------------------------------------------------------------
+constexpr int kChunk = 32;  // sigma points per P_xz tile
+
+__global__ __launch_bounds__(kThreads) void k_update(
+    const float* __restrict__ mean, const float* __restrict__ S, const float* __restrict__ xp,
+    const float* __restrict__ zp, const float* __restrict__ zmean, const float* __restrict__ Sz,
+    const float* __restrict__ obs, float* __restrict__ mean_out, float* __restrict__ tril_out,
+    int* __restrict__ status, int64_t N, int n, int dz, float wc0, float wi, int groups) {
+  __shared__ float T[kMaxDim * kLd];   // P_xz tiles (2 x 32 x 64), later S- / S+ staging
+  __shared__ float P[kMaxDim * kLd];   // P_xz, then U = P_xz S_z^-T in place
+  __shared__ float Zt[kMaxDim * kLd];  // S_z
+  const int64_t f = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const Rows rows(f, N, groups, n);
+  const int ns1 = 2 * n + 1;
+  float* Xc = T;
+  float* Zc = T + kChunk * kMaxDim;
+
+  for (int idx = tid; idx < kMaxDim * kLd; idx += kThreads) Zt[idx] = 0.f;
+  __syncthreads();
+  {
+    const float* Szf = Sz + f * dz * dz;
+    for (int idx = tid; idx < dz * dz; idx += kThreads) {
+      const int j = idx / dz, c = idx % dz;
+      if (c <= j) Zt[j * kLd + c] = Szf[idx];
+    }
+  }
+
+  // P_xz[i][j] = sum_s wc_s (X_s - m)[i] (Z_s - zhat)[j]; thread -> i = ti + 16 a, j = tj + 16 b
+  const float mx = lane < n ? mean[f * n + lane] : 0.f;
+  const float mz = lane < dz ? zmean[f * dz + lane] : 0.f;
+  const int ti = tid >> 4, tj = tid & 15;
+  float acc[4][4] = {};
+  for (int s0 = 0; s0 < ns1; s0 += kChunk) {
+    __syncthreads();
+    for (int t = w; t < kChunk; t += kWaves) {
+      const int s = s0 + t;
+      float xv = 0.f, zv = 0.f;
+      if (s < ns1) {
+        const int64_t r = rows.row(s);
+        const float wgt = s == 0 ? wc0 : wi;
+        if (lane < n) xv = wgt * (xp[r * n + lane] - mx);
+        if (lane < dz) zv = zp[r * dz + lane] - mz;
+      }
+      Xc[t * kMaxDim + lane] = xv;
+      Zc[t * kMaxDim + lane] = zv;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int t = 0; t < kChunk; ++t) {
+      float xa[4], zb[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) xa[a] = Xc[t * kMaxDim + ti + 16 * a];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) zb[b] = Zc[t * kMaxDim + tj + 16 * b];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = fmaf(xa[a], zb[b], acc[a][b]);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) P[(ti + 16 * a) * kLd + tj + 16 * b] = acc[a][b];
+  __syncthreads();  // tiles consumed: T becomes the staging tile of S-
+  {
+    const float* Sf = S + f * n * n;
+    for (int idx = tid; idx < n * n; idx += kThreads) T[(idx / n) * kLd + idx % n] = Sf[idx];
+  }
+  __syncthreads();
+
+  if (w == 0) {
+    // U S_z^T = P_xz, row `lane` of U by forward substitution (rows are independent)
+    for (int j = 0; j < dz; ++j) {
+      float a = P[lane * kLd + j];
+      for (int c = 0; c < j; ++c) a = fmaf(-P[lane * kLd + c], Zt[j * kLd + c], a);
+      P[lane * kLd + j] = a / Zt[j * kLd + j];
+    }
+    // S_z y = z - zhat; lane c ends up holding y_c
+    float v = lane < dz ? obs[f * dz + lane] - mz : 0.f;
+    for (int c = 0; c < dz; ++c) {
+      const float yc = __shfl(v, c) / Zt[c * kLd + c];
+      if (lane > c) v = fmaf(-yc, Zt[lane * kLd + c], v);
+      if (lane == c) v = yc;
+    }
+    float mnew = mx;
+    for (int c = 0; c < dz; ++c) mnew = fmaf(P[lane * kLd + c], __shfl(v, c), mnew);
+    if (lane < n) mean_out[f * n + lane] = mnew;
+
+    float row[kMaxDim];
+#pragma unroll
+    for (int k = 0; k < kMaxDim; ++k)
+      row[k] = (lane < n && k <= lane && k < n) ? T[lane * kLd + k] : 0.f;
+    int flag = 0;
+    for (int c = 0; c < dz; ++c) {
+      const float x = lane < n ? P[lane * kLd + c] : 0.f;
+      chol_rank1<-1>(row, x, n, lane, flag);
+    }
+#pragma unroll
+    for (int k = 0; k < kMaxDim; ++k) T[lane * kLd + k] = row[k];
+    if (lane == 0) status[f] = flag;
+  }
+  __syncthreads();
+  float* So = tril_out + f * n * n;
+  for (int idx = tid; idx < n * n; idx += kThreads) So[idx] = T[(idx / n) * kLd + idx % n];
+}
+
+#define UKF_GEO_CHECK(what, dimname, dim)                                                       \
+  BPK_REQUIRE(N >= 0 && N < (1ll << 31), "%s: N = %lld out of range", what, (long long)N);      \
+  BPK_REQUIRE(n >= 1 && n <= kMaxDim, "%s: n = %d out of range [1, %d]", what, n, kMaxDim);     \
+  BPK_REQUIRE(dim >= 1 && dim <= kMaxDim, "%s: %s = %d out of range [1, %d]", what, dimname,    \
+              dim, kMaxDim);                                                                    \
+  BPK_REQUIRE(groups >= 1 && N % groups == 0, "%s: groups = %d does not divide N = %lld", what, \
+              groups, (long long)N)
+
+#define UKF_PTR(what, p) BPK_REQUIRE(p != nullptr, "%s: %s is NULL", what, #p)
+
+}  // namespace
+
+extern "C" int bpk_ukf_sigma_points_f32(const float* mean, const float* scale_tril,
+                                        float* points, int64_t N, int n, float gamma, int groups,
+                                        void* stream) {
+  UKF_GEO_CHECK("ukf_sigma_points", "n", n);
+  UKF_PTR("ukf_sigma_points", mean);
+  UKF_PTR("ukf_sigma_points", scale_tril);
+  UKF_PTR("ukf_sigma_points", points);
+  if (N == 0) return BPK_OK;
+  hipLaunchKernelGGL(k_sigma, dim3((unsigned)N), dim3(kThreads), 0, bpk::as_stream(stream), mean,
+                     scale_tril, points, N, n, gamma, groups);
+  BPK_LAUNCH_CHECK("ukf_sigma_points");
+  return BPK_OK;
+}
+
+extern "C" int bpk_ukf_root_f32(const float* points, const float* noise_tril, float* mean,
+                                float* scale_tril, int* status, int64_t N, int n, int d,
+                                float wm0, float wc0, float wi, int groups, void* stream) {
+  UKF_GEO_CHECK("ukf_root", "d", d);
+  BPK_REQUIRE(wi > 0.f, "ukf_root: wi = %g must be positive", (double)wi);
+  UKF_PTR("ukf_root", points);
+  UKF_PTR("ukf_root", noise_tril);
+  UKF_PTR("ukf_root", mean);
+  UKF_PTR("ukf_root", scale_tril);
+  UKF_PTR("ukf_root", status);
+  if (N == 0) return BPK_OK;
+  hipLaunchKernelGGL(k_root, dim3((unsigned)N), dim3(kThreads), 0, bpk::as_stream(stream), points,
+                     noise_tril, mean, scale_tril, status, N, n, d, wm0, wc0, wi, groups);
+  BPK_LAUNCH_CHECK("ukf_root");
+  return BPK_OK;
+}
+
+extern "C" int bpk_ukf_update_f32(const float* mean, const float* scale_tril,
+                                  const float* x_points, const float* z_points,
+                                  const float* z_mean, const float* z_tril, const float* obs,
+                                  float* mean_out, float* scale_tril_out, int* status, int64_t N,
+                                  int n, int dz, float wc0, float wi, int groups, void* stream) {
+  UKF_GEO_CHECK("ukf_update", "dz", dz);
+  UKF_PTR("ukf_update", mean);
+  UKF_PTR("ukf_update", scale_tril);
+  UKF_PTR("ukf_update", x_points);
+  UKF_PTR("ukf_update", z_points);
+  UKF_PTR("ukf_update", z_mean);
+  UKF_PTR("ukf_update", z_tril);
+  UKF_PTR("ukf_update", obs);
+  UKF_PTR("ukf_update", mean_out);
+  UKF_PTR("ukf_update", scale_tril_out);
+  UKF_PTR("ukf_update", status);
+  if (N == 0) return BPK_OK;
+  hipLaunchKernelGGL(k_update, dim3((unsigned)N), dim3(kThreads), 0, bpk::as_stream(stream), mean,
+                     scale_tril, x_points, z_points, z_mean, z_tril, obs, mean_out,
+                     scale_tril_out, status, N, n, dz, wc0, wi, groups);
+  BPK_LAUNCH_CHECK("ukf_update");
+  return BPK_OK;
+}

@@ -691,6 +691,40 @@ int bpk_instance_norm_act_bwd2_f64(const double* v, const double* dy, const doub
                                    const double* mean, const double* rstd, double* gdy, double* gx,
                                    int64_t planes, int64_t M, int act, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * ukf: square-root unscented Kalman filter (Van der Merwe & Wan 2001, Merwe scaled
+ * sigma points) over N independent filters, float32, 1 <= n <= 64 (state dimension),
+ * 1 <= d, dz <= 64 (dimension of the propagated points / of the observation).  Stands in
+ * for torchfilter's SquareRootUnscentedKalmanFilter behind the reference's
+ * pinn_kalman/ukf.py:9-44.  Factors are lower triangular [N, dim, dim] row-major; output
+ * factors have a positive diagonal and exact zeros above it.
+ * Point tensors are 2-D [groups * (2n+1) * N/groups, dim] with rows ordered (g, s, r):
+ * filter i = g * (N/groups) + r has sigma point s at row (g * (2n+1) + s) * (N/groups) + r
+ * (groups must divide N; groups = 1 is sigma-major).
+ *   sigma_points: X_0 = m, X_i = m + gamma S[:, i-1], X_{n+i} = m - gamma S[:, i-1].
+ *   root  : mean = wm0 Y_0 + wi sum_{s>=1} Y_s;  scale_tril = the factor with
+ *           S S^T = wc0 D_0 D_0^T + wi sum_{s>=1} D_s D_s^T + R R^T (D_s = Y_s - mean, R =
+ *           the lower triangle of noise_tril [N, d, d]): Householder QR of
+ *           [sqrt(wi) D_1 .. D_2n ; R^T], then one rank-1 update (wc0 > 0) or downdate
+ *           (wc0 < 0) by sqrt|wc0| D_0.  wi > 0.
+ *   update: P_xz = sum_s wc_s (X_s - m)(Z_s - zhat)^T, U = P_xz S_z^-T (= K S_z),
+ *           m+ = m + U S_z^-1 (z - zhat) (= m + K (z - zhat)), S+ = S after one rank-1
+ *           downdate per column of U.
+ * status [N] int32 is written 0, or 1 where a downdate met S_kk^2 - x_k^2 <= 0: that
+ * diagonal becomes eps_f32 |S_kk|, the rest of that vector is dropped, the filter's
+ * outputs are finite but otherwise unspecified, and other filters are unaffected.
+ * No scratch, no atomics (bit-reproducible), asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+int bpk_ukf_sigma_points_f32(const float* mean, const float* scale_tril, float* points, int64_t N,
+                             int n, float gamma, int groups, void* stream);
+int bpk_ukf_root_f32(const float* points, const float* noise_tril, float* mean, float* scale_tril,
+                     int* status, int64_t N, int n, int d, float wm0, float wc0, float wi,
+                     int groups, void* stream);
+int bpk_ukf_update_f32(const float* mean, const float* scale_tril, const float* x_points,
+                       const float* z_points, const float* z_mean, const float* z_tril,
+                       const float* obs, float* mean_out, float* scale_tril_out, int* status,
+                       int64_t N, int n, int dz, float wc0, float wi, int groups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
