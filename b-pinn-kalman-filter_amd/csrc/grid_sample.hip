@@ -327,8 +327,10 @@ int grad2_impl(const T* g2i, const T* g2g, const T* gout, const T* input, const 
                T* gin, T* ggrid, int N, int C, int H_in, int W_in, int H_out, int W_out,
                int padding_mode, int align_corners, void* stream) {
   GS_CHECK();
-  BPK_REQUIRE(ggo && gin && ggrid, "grid_sample2d_grad2: all outputs required");
   const int64_t total = (int64_t)N * H_out * W_out;
+  // an output without elements (N, C or an output extent of 0) has no storage to point at
+  BPK_REQUIRE((ggo || total * C == 0) && (gin || (int64_t)N * C == 0) && (ggrid || total == 0),
+              "grid_sample2d_grad2: all outputs required");
   if (total == 0) return BPK_OK;
   const int S = slices_for(C);
   const unsigned blocks = (unsigned)bpk::ceil_div(total, 256 / S);

@@ -234,6 +234,8 @@ int grad2_3(const T* g2i, const T* g2g, const T* gout, const T* input, const T* 
             int padding_mode, int align_corners, void* stream) {
   GS3_CHECK();
   BPK_REQUIRE(ggo && gin && ggrid, "grid_sample3d_grad2: all outputs required");
+  // unlike the 2-D entry, the kernel reads both unconditionally (the caller materialises zeros)
+  BPK_REQUIRE(g2i && g2g, "grid_sample3d_grad2: g2_input and g2_grid required (no NULL = zeros)");
   const int64_t total = (int64_t)N * Do * Ho * Wo;
   if (total == 0) return BPK_OK;
   hipLaunchKernelGGL(gs3_grad2<T>, dim3(blocks3(total)), dim3(256), 0, bpk::as_stream(stream), g2i,

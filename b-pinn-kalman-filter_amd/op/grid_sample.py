@@ -169,6 +169,9 @@ def grid_sample3d_grad2_raw(g2_input, g2_grid, grad_out, input, grid, padding_mo
     g2_input, g2_grid, grad_out, input, grid = (
         t.contiguous() for t in (g2_input, g2_grid, grad_out, input, grid))
     N, C, D, H, W, Do, Ho, Wo = _geom3(input, grid)
+    if input.numel() == 0 or grid.numel() == 0:
+        # nothing is sampled; the 3-D entry refuses the NULL pointers of empty tensors
+        return torch.zeros_like(grad_out), torch.zeros_like(input), torch.zeros_like(grid)
     ggo = torch.empty_like(grad_out)
     gi = torch.zeros_like(input)
     gg = torch.empty_like(grid)

@@ -121,7 +121,9 @@ int bpk_grid_sample2d_grad2_f64(const double* g2_input, const double* g2_grid,
  * aten::grid_sampler_3d_backward as op/grid_sample.py:79-113 calls them, and
  * gridsample_grad2.grad2_3d (op/grid_sample.cpp:42-57, op/grid_sample_kernel.cu:212-533,
  * host 601-666).  input [N, C, D, H, W], grid [N, Do, Ho, Wo, 3] (x, y, z), contiguous;
- * same output conventions as the 2-D entries (grad_input zero-filled by the caller).
+ * same output conventions as the 2-D entries (grad_input zero-filled by the caller),
+ * with one difference: grad2 takes no NULL g2_input / g2_grid (status 1, checked before
+ * anything else runs; the caller passes explicit zeros for a None).
  * ------------------------------------------------------------------------- */
 int bpk_grid_sample3d_fwd_f32(const float* input, const float* grid, float* out, int N, int C,
                               int D, int H, int W, int Do, int Ho, int Wo, int padding_mode,
