@@ -35,10 +35,52 @@ struct GemmGeo {
                // stores its raw partial to Y + s * N * M * P (gemm_splitk_reduce_kernel adds)
 };
 
+// a / b correctly rounded from r = 1 / b (conv_winograd.hip's div_rn: the residual tail's
+// division, bit for bit the `/` of residual_rescale_kernel)
+__device__ inline float div_rn(float a, float b, float r) {
+  const float q = a * r;
+  return fmaf(fmaf(-q, b, a), r, q);
+}
+
+template <int CTRL>
+__device__ inline float dpp_f(float v) {
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+
+// Chan merge of two partials of c values each; symmetric, so both partners get the same bits
+__device__ inline void merge_stats(float& m, float& m2, float mo, float m2o, float c) {
+  const float d = mo - m;
+  m2 = (m2 + m2o) + d * d * (0.5f * c);
+  m = 0.5f * (m + mo);
+}
+
+// (mean, M2) of 4 values
+__device__ inline void stats4(float a, float b, float c, float d, float& m, float& m2) {
+  m = ((a + b) + (c + d)) * 0.25f;
+  m2 = fmaf(d - m, d - m, fmaf(c - m, c - m, fmaf(b - m, b - m, (a - m) * (a - m))));
+}
+
+// butterfly over the 16 lanes of a DPP row, 4 values per lane in: every lane ends with the
+// (mean, M2) of the row's 64 values (xor 1, xor 2, then the 8- and 16-lane mirrors)
+__device__ inline void merge_row16(float& m, float& m2) {
+  merge_stats(m, m2, dpp_f<0xB1>(m), dpp_f<0xB1>(m2), 4.f);
+  merge_stats(m, m2, dpp_f<0x4E>(m), dpp_f<0x4E>(m2), 8.f);
+  merge_stats(m, m2, dpp_f<0x141>(m), dpp_f<0x141>(m2), 16.f);
+  merge_stats(m, m2, dpp_f<0x140>(m), dpp_f<0x140>(m2), 32.f);
+}
+
+constexpr int kStatCount = 128;  // pixels per GroupNorm partial record (op.conv.GN_PART_COUNT)
+
+// TAIL: the store is (skip + (acc + bias)) / div (skip may be NULL: plain store) and, with
+// stats, every 128 stored pixels of a row leave one (mean, M2) record in
+// stats[n][m][p / 128] -- the layout of bpk_group_norm_chunk_partials_f32.  ksplit == 1 only
+// (under split-K the tail belongs to gemm_splitk_reduce_kernel).
+template <bool TAIL>
 __global__ __launch_bounds__(256, 2) void gemm_nchw_kernel(
     const float* __restrict__ W1, const float* __restrict__ X1, const float* __restrict__ W2,
     const float* __restrict__ X2, const float* __restrict__ bias, float* __restrict__ Y,
-    GemmGeo g, int xcd_remap) {
+    GemmGeo g, int xcd_remap, const float* __restrict__ skip, float div,
+    float2* __restrict__ stats) {
   __shared__ __attribute__((aligned(16))) float sA[2][kBM * kAS];  // 2 x 10 KB
   __shared__ __attribute__((aligned(16))) float sB[2][kKC * kBS];  // 2 x 8.4 KB
 
@@ -141,6 +183,58 @@ __global__ __launch_bounds__(256, 2) void gemm_nchw_kernel(
       const int m = m0 + 64 * wm + 16 * i + 4 * kq + rr;
       bbv[i][rr] = (bias && m < g.M) ? bias[m] : 0.f;
     }
+  if constexpr (TAIL) {
+    // the tiles are free after the loop's last barrier: sA holds wave column 1's row records
+    float2* red = reinterpret_cast<float2*>(&sA[0][0]);  // [128 rows of the tile]
+    const float rdiv = 1.f / div;
+    const float* sn = skip ? skip + (int64_t)n * g.M * g.P : nullptr;
+    float mm[4][4], qq[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (m0 + 64 * wm + 16 * i >= g.M) continue;  // M % 16 == 0: whole 16-row blocks, per wave
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int m = m0 + 64 * wm + 16 * i + 4 * kq + rr;
+        const int64_t o = (int64_t)m * g.P + p0 + 64 * wp + jj;
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = acc[i][j][rr] + bbv[i][rr];
+        if (sn) {
+          float sk[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) sk[j] = sn[o + 16 * j];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = div_rn(sk[j] + v[j], div, rdiv);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) yn[o + 16 * j] = v[j];
+        if (stats) {
+          stats4(v[0], v[1], v[2], v[3], mm[i][rr], qq[i][rr]);
+          merge_row16(mm[i][rr], qq[i][rr]);  // this wave's 64 pixels of row m
+          if (wp == 1 && jj == 0)
+            red[64 * wm + 16 * i + 4 * kq + rr] = make_float2(mm[i][rr], qq[i][rr]);
+        }
+      }
+    }
+    if (stats) {  // kernel-uniform
+      __syncthreads();
+      if (wp == 0 && jj == 0) {
+        const int R = g.P / kStatCount;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (m0 + 64 * wm + 16 * i >= g.M) continue;
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            const int ml = 64 * wm + 16 * i + 4 * kq + rr;
+            const float2 o = red[ml];
+            merge_stats(mm[i][rr], qq[i][rr], o.x, o.y, 64.f);
+            stats[((int64_t)n * g.M + m0 + ml) * R + tp] = make_float2(mm[i][rr], qq[i][rr]);
+          }
+        }
+      }
+    }
+    return;
+  }
   // a whole 128-row tile in range (every NCSN++ / DDPM++ shape): one straight-line store
   // block -- the per-row guard put each store group in its own branch, and the wait counter
   // (vmcnt counts stores on gfx9) was drained to 0 at every one of them
@@ -169,12 +263,19 @@ __global__ __launch_bounds__(256, 2) void gemm_nchw_kernel(
 }
 
 
-// y[n][m][p] = sum_s part[s][n][m][p] + bias[m] (fixed order), 4 pixels per thread
+// y[n][m][p] = sum_s part[s][n][m][p] + bias[m] (fixed order), 4 pixels per thread.
+// TAIL: the residual tail and the GroupNorm partial records of the stored values, as the
+// TAIL epilogue of gemm_nchw_kernel (a record = the 32 consecutive threads of 128 pixels;
+// slab4 is a multiple of 256, so every wave is whole).
+template <bool TAIL>
 __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const f4* __restrict__ part,
                                                                  int S, int64_t slab4,
                                                                  const float* __restrict__ bias,
                                                                  f4* __restrict__ y, int M,
-                                                                 int P4) {
+                                                                 int P4,
+                                                                 const f4* __restrict__ skip,
+                                                                 float div,
+                                                                 float2* __restrict__ stats) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= slab4) return;
   f4 v = part[i];
@@ -183,7 +284,24 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const f4* __res
     const float b = bias[(int)((i / P4) % M)];
     v += f4{b, b, b, b};
   }
+  if constexpr (TAIL) {
+    if (skip) {
+      const f4 sk = skip[i];
+      const float rdiv = 1.f / div;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = div_rn(sk[c] + v[c], div, rdiv);
+    }
+  }
   y[i] = v;
+  if constexpr (TAIL) {
+    if (stats) {
+      float m, m2;
+      stats4(v[0], v[1], v[2], v[3], m, m2);
+      merge_row16(m, m2);
+      merge_stats(m, m2, __shfl_xor(m, 16, 64), __shfl_xor(m2, 16, 64), 64.f);
+      if ((threadIdx.x & 31) == 0) stats[i >> 5] = make_float2(m, m2);
+    }
+  }
 }
 
 
@@ -380,9 +498,9 @@ extern "C" int bpk_gemm_nchw_f32(const float* W, int ldw, const float* X1, int K
   const int64_t blocks = (int64_t)N * g.tiles_m * g.tiles_p;
   BPK_REQUIRE(blocks < (1LL << 31), "gemm_nchw: grid too large");
   const int remap = (blocks % 8 == 0) ? 1 : 0;
-  hipLaunchKernelGGL(gemm_nchw_kernel, dim3((unsigned)blocks), dim3(256), 0,
+  hipLaunchKernelGGL(gemm_nchw_kernel<false>, dim3((unsigned)blocks), dim3(256), 0,
                      bpk::as_stream(stream), W, X1, K2 ? W + K1 : W, K2 ? X2 : X1, bias, Y, g,
-                     remap);
+                     remap, (const float*)nullptr, 1.f, (float2*)nullptr);
   BPK_LAUNCH_CHECK("gemm_nchw");
   return BPK_OK;
 }
@@ -410,11 +528,12 @@ extern "C" int64_t bpk_gemm_nchw_splitk_bytes(int N, int M, int P, int K1, int K
   return S > 1 ? (int64_t)S * N * M * P * (int64_t)sizeof(float) : 0;
 }
 
-extern "C" int bpk_gemm_nchw_splitk_f32(const float* W, int ldw, const float* X1, int K1,
-                                        const float* X2, int K2, const float* bias, float* Y,
-                                        float* workspace, int N, int M, int P, void* stream) {
-  const int S = gemm_splits(N, M, P, K1, K2);
-  if (S <= 1) return bpk_gemm_nchw_f32(W, ldw, X1, K1, X2, K2, bias, Y, N, M, P, stream);
+// the split-K launches; the reduce carries the tail (skip / stats) when TAIL
+template <bool TAIL>
+static int gemm_splitk_launch(const float* W, int ldw, const float* X1, int K1, const float* X2,
+                              int K2, const float* bias, const float* skip, float div, float* Y,
+                              float* stats, float* workspace, int N, int M, int P, int S,
+                              void* stream) {
   BPK_REQUIRE(ldw >= K1 + K2 && ldw % 4 == 0, "gemm_nchw: bad weight row stride %d", ldw);
   BPK_REQUIRE(K2 == 0 || X2 != nullptr, "gemm_nchw: K2 > 0 needs X2");
   BPK_REQUIRE(workspace != nullptr, "gemm_nchw_splitk: workspace is NULL");
@@ -422,15 +541,52 @@ extern "C" int bpk_gemm_nchw_splitk_f32(const float* W, int ldw, const float* X1
   const int64_t blocks = (int64_t)N * g.tiles_m * g.tiles_p * S;
   BPK_REQUIRE(blocks < (1LL << 31), "gemm_nchw: grid too large");
   hipStream_t st = bpk::as_stream(stream);
-  hipLaunchKernelGGL(gemm_nchw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, W, X1,
-                     K2 ? W + K1 : W, K2 ? X2 : X1, nullptr, workspace, g,
-                     (blocks % 8 == 0) ? 1 : 0);
+  hipLaunchKernelGGL(gemm_nchw_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, W, X1,
+                     K2 ? W + K1 : W, K2 ? X2 : X1, (const float*)nullptr, workspace, g,
+                     (blocks % 8 == 0) ? 1 : 0, (const float*)nullptr, 1.f, (float2*)nullptr);
   BPK_LAUNCH_CHECK("gemm_nchw_splitk");
   const int64_t slab4 = (int64_t)N * M * P / 4;
-  hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)bpk::ceil_div(slab4, 256)),
+  hipLaunchKernelGGL(gemm_splitk_reduce_kernel<TAIL>, dim3((unsigned)bpk::ceil_div(slab4, 256)),
                      dim3(256), 0, st, reinterpret_cast<const f4*>(workspace), S, slab4, bias,
-                     reinterpret_cast<f4*>(Y), M, P / 4);
+                     reinterpret_cast<f4*>(Y), M, P / 4, reinterpret_cast<const f4*>(skip), div,
+                     reinterpret_cast<float2*>(stats));
   BPK_LAUNCH_CHECK("gemm_nchw_splitk_reduce");
+  return BPK_OK;
+}
+
+extern "C" int bpk_gemm_nchw_splitk_f32(const float* W, int ldw, const float* X1, int K1,
+                                        const float* X2, int K2, const float* bias, float* Y,
+                                        float* workspace, int N, int M, int P, void* stream) {
+  const int S = gemm_splits(N, M, P, K1, K2);
+  if (S <= 1) return bpk_gemm_nchw_f32(W, ldw, X1, K1, X2, K2, bias, Y, N, M, P, stream);
+  return gemm_splitk_launch<false>(W, ldw, X1, K1, X2, K2, bias, nullptr, 1.f, Y, nullptr,
+                                   workspace, N, M, P, S, stream);
+}
+
+extern "C" int bpk_gemm_nchw_ex_f32(const float* W, int ldw, const float* X1, int K1,
+                                    const float* X2, int K2, const float* bias,
+                                    const float* skip, float div, float* Y, float* stats,
+                                    float* workspace, int N, int M, int P, void* stream) {
+  BPK_REQUIRE(bpk_gemm_nchw_supported(N, M, P, K1, K2),
+              "gemm_nchw_ex: unsupported shape N=%d M=%d P=%d K1=%d K2=%d (need M %% 16, "
+              "P %% 128, K %% 16 == 0)", N, M, P, K1, K2);
+  BPK_REQUIRE(ldw >= K1 + K2 && ldw % 4 == 0, "gemm_nchw_ex: bad weight row stride %d", ldw);
+  BPK_REQUIRE(K2 == 0 || X2 != nullptr, "gemm_nchw_ex: K2 > 0 needs X2");
+  BPK_REQUIRE(skip == nullptr || div != 0.f, "gemm_nchw_ex: div is 0");
+  BPK_REQUIRE(skip == nullptr || (reinterpret_cast<uintptr_t>(skip) & 15) == 0,
+              "gemm_nchw_ex: skip must be 16-byte aligned");
+  BPK_REQUIRE(Y != skip && Y != X1 && Y != X2, "gemm_nchw_ex: Y aliases an input");
+  const int S = workspace ? gemm_splits(N, M, P, K1, K2) : 1;
+  if (S > 1)
+    return gemm_splitk_launch<true>(W, ldw, X1, K1, X2, K2, bias, skip, div, Y, stats, workspace,
+                                    N, M, P, S, stream);
+  GemmGeo g{N, M, P, K1, K2, ldw, (M + kBM - 1) / kBM, P / kBP, 1};
+  const int64_t blocks = (int64_t)N * g.tiles_m * g.tiles_p;
+  BPK_REQUIRE(blocks < (1LL << 31), "gemm_nchw_ex: grid too large");
+  hipLaunchKernelGGL(gemm_nchw_kernel<true>, dim3((unsigned)blocks), dim3(256), 0,
+                     bpk::as_stream(stream), W, X1, K2 ? W + K1 : W, K2 ? X2 : X1, bias, Y, g,
+                     (blocks % 8 == 0) ? 1 : 0, skip, div, reinterpret_cast<float2*>(stats));
+  BPK_LAUNCH_CHECK("gemm_nchw_ex");
   return BPK_OK;
 }
 

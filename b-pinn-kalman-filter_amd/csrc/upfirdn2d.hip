@@ -211,6 +211,9 @@ int launch_tiled_w(const T* x, const T* k, T* out, int major, int in_h, int in_w
                                               out_h, out_w, st);
 }
 
+// The Winograd conv prologue's SiLU (csrc/conv_winograd.hip silu_f), for the PRE forms below
+__device__ inline float silu_f(float z) { return z * __builtin_amdgcn_rcpf(1.f + __expf(-z)); }
+
 // Register-streaming kernel for the FIR modes NCSN++ uses (and their adjoints):
 // (up, down) in {(1,2), (1,1), (2,1)}, taps <= 4x4, pad0 = P0 on both axes.  A lane segment of
 // SEGW lanes (SEGW = 64 / 32 / 16 / 8, matched to the plane width so no lane idles) owns a
@@ -225,16 +228,22 @@ int launch_tiled_w(const T* x, const T* k, T* out, int major, int in_h, int in_w
 // of conv_downsample_2d, 64 -> 65): the segment's last lane also produces the plane's last
 // column from the values it already holds, so a 65-wide row takes a 32-lane segment
 // instead of a half-idle 64-lane one.
+// PRE: the filtered image is silu(x * s + t) with (s, t) = pre[plane] (GroupNorm + SiLU of a
+// residual block applied while loading, as the Winograd conv's prologue); the activation is
+// applied to loaded samples only, so a tap outside the plane still contributes 0 (the padding
+// is zero AFTER the activation), and the neighbours' values arrive activated by the shuffles.
 #ifndef UPFIRDN_WPE
 #define UPFIRDN_WPE 1
 #endif
-template <int UP, int DOWN, int P0, int R, int SEGW, int NOCD = 0, bool TAIL = false>
+template <int UP, int DOWN, int P0, int R, int SEGW, int NOCD = 0, bool TAIL = false,
+          bool PRE = false>
 __global__ __launch_bounds__(256, UPFIRDN_WPE) void upfirdn2d_stream(const float* __restrict__ x,
                                                          const float* __restrict__ kern,
                                                          float* __restrict__ out, int in_h,
                                                          int in_w, int kh, int kw, int out_h,
                                                          int out_w, int strips_x, int strips_y,
-                                                         int64_t n_strips) {
+                                                         int64_t n_strips,
+                                                         const float2* __restrict__ pre) {
   // output columns per lane: NOCD, or the default 1 (down2) / 2
   constexpr int NOC = NOCD > 0 ? NOCD : ((UP == 1 && DOWN == 2) ? 1 : 2);
   constexpr int LV = NOC * DOWN / UP;                      // input columns loaded per lane
@@ -269,6 +278,8 @@ __global__ __launch_bounds__(256, UPFIRDN_WPE) void upfirdn2d_stream(const float
     for (int oc = 0; oc < NOCT; ++oc) acc[r][oc] = 0.f;
 
   const float* xp = x + plane * in_h * in_w;
+  float2 st = make_float2(1.f, 0.f);
+  if constexpr (PRE) st = pre[plane];
 #pragma unroll
   for (int t = 0; t < NIR; ++t) {
     const int iy = iy_lo + t;
@@ -298,6 +309,11 @@ __global__ __launch_bounds__(256, UPFIRDN_WPE) void upfirdn2d_stream(const float
     } else {
       own[0] = (row_ok && mycol < in_w) ? row[mycol] : 0.f;
     }
+    if constexpr (PRE) {  // loaded samples only: what lies outside the plane stays 0
+#pragma unroll
+      for (int c = 0; c < LV; ++c)
+        own[c] = (row_ok && mycol + c < in_w) ? silu_f(own[c] * st.x + st.y) : 0.f;
+    }
 #pragma unroll
     for (int c = 0; c < LV; ++c) {
       left[c] = __shfl_up(own[c], 1, SEGW);
@@ -307,14 +323,18 @@ __global__ __launch_bounds__(256, UPFIRDN_WPE) void upfirdn2d_stream(const float
 #pragma unroll
       for (int c = 0; c < LV; ++c) {
         const int col = mycol - LV + c;
-        left[c] = (row_ok && col >= 0 && col < in_w) ? row[col] : 0.f;
+        const bool ok = row_ok && col >= 0 && col < in_w;
+        left[c] = ok ? row[col] : 0.f;
+        if constexpr (PRE) left[c] = ok ? silu_f(left[c] * st.x + st.y) : 0.f;
       }
     }
     if (sl == SEGW - 1) {
 #pragma unroll
       for (int c = 0; c < LV; ++c) {
         const int col = mycol + LV + c;
-        right[c] = (row_ok && col < in_w) ? row[col] : 0.f;
+        const bool ok = row_ok && col < in_w;
+        right[c] = ok ? row[col] : 0.f;
+        if constexpr (PRE) right[c] = ok ? silu_f(right[c] * st.x + st.y) : 0.f;
       }
     }
 #pragma unroll
@@ -383,9 +403,10 @@ __global__ __launch_bounds__(256, UPFIRDN_WPE) void upfirdn2d_stream(const float
   }
 }
 
-template <int UP, int DOWN, int P0, int R, int SEGW, int NOCD, bool TAIL = false>
+template <int UP, int DOWN, int P0, int R, int SEGW, int NOCD, bool TAIL = false, bool PRE = false>
 int launch_stream_seg(const float* x, const float* k, float* out, int major, int in_h, int in_w,
-                      int kh, int kw, int out_h, int out_w, hipStream_t st) {
+                      int kh, int kw, int out_h, int out_w, hipStream_t st,
+                      const float2* pre = nullptr) {
   constexpr int NOC = NOCD > 0 ? NOCD : ((UP == 1 && DOWN == 2) ? 1 : 2);
   const int strips_x = TAIL ? 1 : (int)bpk::ceil_div(out_w, SEGW * NOC);
   const int strips_y = (int)bpk::ceil_div(out_h, R);
@@ -393,25 +414,26 @@ int launch_stream_seg(const float* x, const float* k, float* out, int major, int
   if (n <= 0) return BPK_OK;
   const int64_t blocks = bpk::ceil_div(n, 4 * (64 / SEGW));
   BPK_REQUIRE(blocks < (int64_t)INT32_MAX, "upfirdn2d: grid too large");
-  hipLaunchKernelGGL((upfirdn2d_stream<UP, DOWN, P0, R, SEGW, NOCD, TAIL>), dim3((unsigned)blocks), dim3(256),
-                     0, st, x, k, out, in_h, in_w, kh, kw, out_h, out_w, strips_x, strips_y, n);
+  hipLaunchKernelGGL((upfirdn2d_stream<UP, DOWN, P0, R, SEGW, NOCD, TAIL, PRE>), dim3((unsigned)blocks), dim3(256),
+                     0, st, x, k, out, in_h, in_w, kh, kw, out_h, out_w, strips_x, strips_y, n, pre);
   BPK_LAUNCH_CHECK("upfirdn2d_stream");
   return BPK_OK;
 }
 
 // segment width = lanes needed for one output row of the plane (power of two, 8..64)
-template <int UP, int DOWN, int P0, int R, int NOCD = 0>
+template <int UP, int DOWN, int P0, int R, int NOCD = 0, bool PRE = false>
 int launch_stream(const float* x, const float* k, float* out, int major, int in_h, int in_w,
-                  int kh, int kw, int out_h, int out_w, hipStream_t st) {
+                  int kh, int kw, int out_h, int out_w, hipStream_t st,
+                  const float2* pre = nullptr) {
   constexpr int NOC = NOCD > 0 ? NOCD : ((UP == 1 && DOWN == 2) ? 1 : 2);
   const int lanes = (int)bpk::ceil_div(out_w, NOC);
   if (lanes <= 8)
-    return launch_stream_seg<UP, DOWN, P0, R, 8, NOCD>(x, k, out, major, in_h, in_w, kh, kw, out_h, out_w, st);
+    return launch_stream_seg<UP, DOWN, P0, R, 8, NOCD, false, PRE>(x, k, out, major, in_h, in_w, kh, kw, out_h, out_w, st, pre);
   if (lanes <= 16)
-    return launch_stream_seg<UP, DOWN, P0, R, 16, NOCD>(x, k, out, major, in_h, in_w, kh, kw, out_h, out_w, st);
+    return launch_stream_seg<UP, DOWN, P0, R, 16, NOCD, false, PRE>(x, k, out, major, in_h, in_w, kh, kw, out_h, out_w, st, pre);
   if (lanes <= 32)
-    return launch_stream_seg<UP, DOWN, P0, R, 32, NOCD>(x, k, out, major, in_h, in_w, kh, kw, out_h, out_w, st);
-  return launch_stream_seg<UP, DOWN, P0, R, 64, NOCD>(x, k, out, major, in_h, in_w, kh, kw, out_h, out_w, st);
+    return launch_stream_seg<UP, DOWN, P0, R, 32, NOCD, false, PRE>(x, k, out, major, in_h, in_w, kh, kw, out_h, out_w, st, pre);
+  return launch_stream_seg<UP, DOWN, P0, R, 64, NOCD, false, PRE>(x, k, out, major, in_h, in_w, kh, kw, out_h, out_w, st, pre);
 }
 
 // Row-rolling kernel for the UP = 1 modes (down2 and the 1:1 FIR), taps <= 4x4: a lane segment
@@ -422,13 +444,15 @@ int launch_stream(const float* x, const float* k, float* out, int major, int in_
 // 10 / 8 rows for the 4-row strips) at ~half the registers.  The next input row's loads are
 // issued before the current row's arithmetic (one row of prefetch).
 //   out row oy reads input rows oy*DOWN - P0 + i, i < 4: input row t feeds tap i = t - oy*DOWN + P0.
-template <int DOWN, int P0, int SEGW, int NOC, bool TAIL, int RB = 0>
+// PRE: as upfirdn2d_stream (silu(x * s + t) of loaded samples, zero outside the plane).
+template <int DOWN, int P0, int SEGW, int NOC, bool TAIL, int RB = 0, bool PRE = false>
 __global__ __launch_bounds__(256) void upfirdn2d_roll(const float* __restrict__ x,
                                                        const float* __restrict__ kern,
                                                        float* __restrict__ out, int in_h,
                                                        int in_w, int kh, int kw, int out_h,
                                                        int out_w, int rows, int strips_x,
-                                                       int strips_y, int64_t n_strips) {
+                                                       int strips_y, int64_t n_strips,
+                                                       const float2* __restrict__ pre) {
   static_assert(DOWN == 1 || DOWN == 2, "upfirdn2d_roll: down 1 or 2");
   constexpr int LV = NOC * DOWN;                 // input columns loaded per lane
   constexpr int NOCT = NOC + (TAIL ? 1 : 0);     // columns computed (tail on the last lane)
@@ -455,6 +479,8 @@ __global__ __launch_bounds__(256) void upfirdn2d_roll(const float* __restrict__ 
       w[i][j] = (i < kh && j < kw) ? kern[(kh - 1 - i) * kw + (kw - 1 - j)] : 0.f;
 
   const float* xp = x + plane * in_h * in_w;
+  float2 st = make_float2(1.f, 0.f);
+  if constexpr (PRE) st = pre[plane];
   // one input row: own LV columns (vector load), the neighbours' by segment shuffles, the
   // segment edges' by direct loads (zero outside the plane)
   auto load_row = [&](int iy, float (&own)[LV]) {
@@ -479,6 +505,11 @@ __global__ __launch_bounds__(256) void upfirdn2d_roll(const float* __restrict__ 
     } else {
       own[0] = (row_ok && mycol < in_w) ? row[mycol] : 0.f;
     }
+    if constexpr (PRE) {  // loaded samples only: what lies outside the plane stays 0
+#pragma unroll
+      for (int c = 0; c < LV; ++c)
+        own[c] = (row_ok && mycol + c < in_w) ? silu_f(own[c] * st.x + st.y) : 0.f;
+    }
   };
   auto edges = [&](int iy, const float (&own)[LV], float (&left)[LV], float (&right)[LV]) {
 #pragma unroll
@@ -492,14 +523,18 @@ __global__ __launch_bounds__(256) void upfirdn2d_roll(const float* __restrict__ 
 #pragma unroll
       for (int c = 0; c < LV; ++c) {
         const int col = mycol - LV + c;
-        left[c] = (row_ok && col >= 0 && col < in_w) ? row[col] : 0.f;
+        const bool ok = row_ok && col >= 0 && col < in_w;
+        left[c] = ok ? row[col] : 0.f;
+        if constexpr (PRE) left[c] = ok ? silu_f(left[c] * st.x + st.y) : 0.f;
       }
     }
     if (sl == SEGW - 1) {
 #pragma unroll
       for (int c = 0; c < LV; ++c) {
         const int col = mycol + LV + c;
-        right[c] = (row_ok && col < in_w) ? row[col] : 0.f;
+        const bool ok = row_ok && col < in_w;
+        right[c] = ok ? row[col] : 0.f;
+        if constexpr (PRE) right[c] = ok ? silu_f(right[c] * st.x + st.y) : 0.f;
       }
     }
   };
@@ -666,17 +701,18 @@ __global__ __launch_bounds__(256) void upfirdn2d_roll(const float* __restrict__ 
   }
 }
 
-template <int DOWN, int P0, int SEGW, int NOC, bool TAIL = false, int RB = 0>
+template <int DOWN, int P0, int SEGW, int NOC, bool TAIL = false, int RB = 0, bool PRE = false>
 int launch_roll(const float* x, const float* k, float* out, int major, int in_h, int in_w, int kh,
-                int kw, int out_h, int out_w, int rows, hipStream_t st) {
+                int kw, int out_h, int out_w, int rows, hipStream_t st,
+                const float2* pre = nullptr) {
   const int strips_x = TAIL ? 1 : (int)bpk::ceil_div(out_w, SEGW * NOC);
   const int strips_y = (int)bpk::ceil_div(out_h, rows);
   const int64_t n = (int64_t)major * strips_x * strips_y;
   if (n <= 0) return BPK_OK;
   const int64_t blocks = bpk::ceil_div(n, 4 * (64 / SEGW));
   BPK_REQUIRE(blocks < (int64_t)INT32_MAX, "upfirdn2d: grid too large");
-  hipLaunchKernelGGL((upfirdn2d_roll<DOWN, P0, SEGW, NOC, TAIL, RB>), dim3((unsigned)blocks), dim3(256),
-                     0, st, x, k, out, in_h, in_w, kh, kw, out_h, out_w, rows, strips_x, strips_y, n);
+  hipLaunchKernelGGL((upfirdn2d_roll<DOWN, P0, SEGW, NOC, TAIL, RB, PRE>), dim3((unsigned)blocks), dim3(256),
+                     0, st, x, k, out, in_h, in_w, kh, kw, out_h, out_w, rows, strips_x, strips_y, n, pre);
   BPK_LAUNCH_CHECK("upfirdn2d_roll");
   return BPK_OK;
 }
@@ -854,6 +890,56 @@ extern "C" int bpk_upfirdn2d_f32(const float* x, const float* kernel, float* out
   return upfirdn2d_impl<float>(x, kernel, out, major, in_h, in_w, minor, kernel_h, kernel_w, up_x,
                                up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, out_h, out_w,
                                stream);
+}
+
+// The forms with a PRE kernel: what the NCSN++ resample blocks select (try_stream / try_roll
+// above, same strip shapes) -- up 2 with pad0 = 2 on the 4-columns-per-lane stream kernel, down
+// 2 with pad0 = 1 on the rolling kernel -- taps <= 4x4, rows of 4 k floats.
+extern "C" int bpk_upfirdn2d_pre_supported(int major, int in_h, int in_w, int kernel_h,
+                                           int kernel_w, int up, int down, int pad0, int pad1) {
+  if (major < 0 || in_h <= 0 || in_w <= 0 || in_w % 4 != 0) return 0;
+  if (kernel_h <= 0 || kernel_w <= 0 || kernel_h > 4 || kernel_w > 4) return 0;
+  const int out_h = (in_h * up + pad0 + pad1 - kernel_h) / (down > 0 ? down : 1) + 1;
+  const int out_w = (in_w * up + pad0 + pad1 - kernel_w) / (down > 0 ? down : 1) + 1;
+  if (out_h <= 0 || out_w <= 0) return 0;
+  if (up == 2 && down == 1) return pad0 == 2 && out_w % 4 == 0;
+  if (up == 1 && down == 2) return pad0 == 1;
+  return 0;
+}
+
+extern "C" int bpk_upfirdn2d_pre_f32(const float* x, const float* pre, const float* kernel,
+                                     float* out, int major, int in_h, int in_w, int kernel_h,
+                                     int kernel_w, int up, int down, int pad0, int pad1,
+                                     int out_h, int out_w, void* stream) {
+  BPK_REQUIRE(bpk_upfirdn2d_pre_supported(major, in_h, in_w, kernel_h, kernel_w, up, down, pad0,
+                                          pad1),
+              "upfirdn2d_pre: no PRE form for in %dx%d taps %dx%d up %d down %d pad (%d,%d)",
+              in_h, in_w, kernel_h, kernel_w, up, down, pad0, pad1);
+  const int exp_h = (in_h * up + pad0 + pad1 - kernel_h) / down + 1;
+  const int exp_w = (in_w * up + pad0 + pad1 - kernel_w) / down + 1;
+  BPK_REQUIRE(out_h == exp_h && out_w == exp_w,
+              "upfirdn2d_pre: out shape (%d,%d) != expected (%d,%d)", out_h, out_w, exp_h, exp_w);
+  if (major == 0) return BPK_OK;  // empty batch: nothing to read or write (pointers may be NULL)
+  BPK_REQUIRE(pre != nullptr, "upfirdn2d_pre: pre is NULL");
+  BPK_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(pre) & 7) == 0,
+              "upfirdn2d_pre: x / out must be 16-byte aligned, pre 8-byte");
+  hipStream_t st = bpk::as_stream(stream);
+  const float2* pr = reinterpret_cast<const float2*>(pre);
+  if (up == 2)
+    return launch_stream<2, 1, 2, 16, 4, true>(x, kernel, out, major, in_h, in_w, kernel_h,
+                                               kernel_w, out_h, out_w, st, pr);
+  const int lanes = (int)bpk::ceil_div(out_w, 2);  // as try_roll: two output columns per lane
+  const int sw = lanes <= 8 ? 8 : lanes <= 16 ? 16 : lanes <= 32 ? 32 : 64;
+  const int rows = roll_rows_down2(major, out_h, (int)bpk::ceil_div(out_w, 2 * sw), 64 / sw);
+#define BPK_ROLL2P(SW)                                                                         \
+  return launch_roll<2, 1, SW, 2, false, 0, true>(x, kernel, out, major, in_h, in_w, kernel_h, \
+                                                  kernel_w, out_h, out_w, rows, st, pr)
+  if (sw == 8) BPK_ROLL2P(8);
+  if (sw == 16) BPK_ROLL2P(16);
+  if (sw == 32) BPK_ROLL2P(32);
+  BPK_ROLL2P(64);
+#undef BPK_ROLL2P
 }
 
 extern "C" int bpk_upfirdn2d_f64(const double* x, const double* kernel, double* out, int major,

@@ -51,21 +51,52 @@ class TembBank:
     launches (and one SiLU instead of one per block).  Under autograd the backward is then
     one GEMM per gradient too (the weight gradients of all blocks in one launch, split back
     into each Dense_0's as views), instead of three launches and an add per block.  Built per
-    forward from the live weights (no cache to go stale when EMA / load_state_dict / an
-    optimizer step rewrite them).  The same values as per-block Linear calls: each output is
+    forward from the live weights; at inference (`owner`) the concatenations are kept between
+    forwards and rebuilt when EMA / load_state_dict / an optimizer step move a parameter's
+    version counter.  The same values as per-block Linear calls: each output is
     the same dot product over the same K order."""
 
-    def __init__(self, temb, act, denses):
+    def __init__(self, temb, act, denses, owner=None, conv_biases=None):
+        """owner (inference only): the module that keeps the concatenated weight and bias
+        between forwards (op.conv.weight_derived: rebuilt when a parameter's version moves);
+        conv_biases: each block's Conv_0.bias, folded into the bank's bias, so a slice is the
+        block's whole per-(n, c) bias Conv_0.bias + Dense_0(act(temb)) (conv_temb_bias)."""
         self._idx = {}
         sizes = []
         for i, d in enumerate(denses):
             self._idx[id(d)] = i
             sizes.append(d.out_features)
-        w = channels.cat([d.weight for d in denses], 0)
-        b = channels.cat([d.bias for d in denses], 0)
+        self.folded = owner is not None and conv_biases is not None
+        if owner is not None:
+            # blocks of equal width side by side: each run of them is regrouped below, in one
+            # copy, into per-block contiguous [N, C] slices (what the GroupNorm kernels read)
+            order = sorted(range(len(denses)), key=lambda i: sizes[i])
+            ws, bs = [denses[i].weight for i in order], [denses[i].bias for i in order]
+            w = conv_op.weight_derived(owner, "temb_bank_w", ws, lambda: channels.cat(ws, 0))
+            if self.folded:
+                cb = [conv_biases[i] for i in order]
+                b = conv_op.weight_derived(owner, "temb_bank_b_folded", bs + cb,
+                                           lambda: channels.cat(bs, 0) + channels.cat(cb, 0))
+            else:
+                b = conv_op.weight_derived(owner, "temb_bank_b", bs, lambda: channels.cat(bs, 0))
+        else:
+            w = channels.cat([d.weight for d in denses], 0)
+            b = channels.cat([d.bias for d in denses], 0)
         a = act(temb)
         allp = (matmul_op.linear(a, w, b) if a.is_cuda and matmul_op.supported(a, w, b)
                 else torch.addmm(b, a, w.t()))
+        if owner is not None:
+            n, parts, off, k = allp.shape[0], [None] * len(denses), 0, 0
+            while k < len(order):
+                c, m = sizes[order[k]], k
+                while m < len(order) and sizes[order[m]] == c:
+                    m += 1
+                buf = allp[:, off:off + (m - k) * c].reshape(n, m - k, c).permute(1, 0, 2).contiguous()
+                for j in range(m - k):
+                    parts[order[k + j]] = buf[j]
+                off, k = off + (m - k) * c, m
+            self.parts = parts
+            return
         # per-block views; under autograd one split (its backward: one concatenation) rather
         # than a slice per block (a zero-filled full-size gradient per slice, then the adds)
         self.parts = channels.split(allp, sizes, 1)
@@ -77,8 +108,28 @@ class TembBank:
 def temb_proj(dense_m: nn.Linear, act, temb):
     """dense(act(temb)) -- a TembBank slice when the forward built one."""
     if isinstance(temb, TembBank):
+        if temb.folded:
+            raise RuntimeError("temb_proj: this TembBank carries the blocks' Conv_0 biases "
+                               "(use conv_temb_bias)")
         return temb.proj(dense_m)
     return dense(dense_m, act(temb))
+
+
+# inference: the concatenated Dense_0 weights / biases of the TembBank kept between forwards,
+# Conv_0.bias folded into the bias; read once at import (with BPK_WEIGHT_CACHE, op.conv)
+_TEMB_FOLD = os.environ.get("BPK_TEMB_FOLD", "1") == "1"
+
+
+def conv_temb_bias(block: nn.Module, act, temb, n):
+    """The per-(n, c) bias that follows a residual block's Conv_0: Conv_0.bias[None, :] +
+    Dense_0(act(temb)) [n, C] (Conv_0.bias alone, broadcast, without temb) -- one TembBank
+    slice when the bank folded the conv bias in."""
+    if isinstance(temb, TembBank) and temb.folded:
+        return temb.proj(block.Dense_0)
+    bias_nc = block.Conv_0.bias[None, :].expand(n, -1)
+    if temb is not None:
+        bias_nc = bias_nc + temb_proj(block.Dense_0, act, temb)
+    return bias_nc
 
 
 _GN_FANOUT = os.environ.get("BPK_GN_FANOUT", "1") == "1"  # A/B switch (gn_act_fanout)

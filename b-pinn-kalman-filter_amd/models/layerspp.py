@@ -12,12 +12,14 @@ Per block the arithmetic is re-scheduled for the GPU:
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from op import conv as conv_op
 from op.norm_act import residual_rescale
 
 from . import layers, up_or_down_sampling
@@ -26,6 +28,16 @@ from . import layers, up_or_down_sampling
 _ATTN_QKV = True
 # ... and softmax(q^T k) v as one fused kernel (csrc/attention.hip; False: bmm + softmax + bmm)
 _ATTN_FUSED = True
+# A/B switches of the inference paths outside the 3x3 convs, read once at import:
+# the attention block's residual tail + GroupNorm partials in the NIN_3 GEMM's store
+_GEMM_TAIL = os.environ.get("BPK_GEMM_TAIL", "1") == "1"
+# up blocks: the 1x1 skip projection (Conv_2) before the FIR upsample, on a quarter of the pixels
+_UP_SKIP_FIRST = os.environ.get("BPK_UP_SKIP_FIRST", "1") == "1"
+# up / down blocks: GroupNorm_0 + SiLU applied inside the FIR resampler's loads (upfirdn2d_pre)
+_FIR_PRE = os.environ.get("BPK_FIR_PRE", "1") == "1"
+# up / down blocks: Conv_0 writes its output's GroupNorm partials (no statistics pass for
+# GroupNorm_1)
+_RESAMPLE_STATS = os.environ.get("BPK_RESAMPLE_STATS", "1") == "1"
 
 conv1x1 = layers.ddpm_conv1x1
 conv3x3 = layers.ddpm_conv3x3
@@ -81,7 +93,7 @@ class AttnBlockpp(nn.Module):
         h = gn_act(x, self.GroupNorm_0, None)
         div = np.sqrt(2.) if self.skip_rescale else 1.0
         if _ATTN_QKV and not torch.is_grad_enabled() and self._qkv_ok(h):
-            return residual_rescale(x, self._forward_qkv(h), None, div)
+            return self._forward_qkv(h, x, div)
         h = self.NIN_3(layers._attention(h, self.NIN_0, self.NIN_1, self.NIN_2))
         return residual_rescale(x, h, None, div)
 
@@ -92,29 +104,42 @@ class AttnBlockpp(nn.Module):
                 and bool(conv_op.lib.bpk_gemm_nchw_supported(N, 3 * C, H * W, C, 0))
                 and bool(conv_op.lib.bpk_gemm_nchw_supported(N, C, H * W, C, 0)))
 
-    def _forward_qkv(self, h):
+    def _forward_qkv(self, h, skip=None, div=1.0):
         """Inference: q, k, v as ONE MFMA GEMM over the stacked NIN weights, NIN_3 as another
         (op.conv.conv1x1), the 1/sqrt(C) scale folded into q's weights when it is a power of
-        two (exact: C = 4^k, e.g. 256) and applied to the logits otherwise."""
+        two (exact: C = 4^k, e.g. 256) and applied to the logits otherwise.  With `skip` the
+        result is the block's output (skip + NIN_3(...)) / div: the residual tail and the
+        output's GroupNorm partial statistics in the NIN_3 GEMM's store (BPK_GEMM_TAIL=0: the
+        separate residual_rescale launch, no statistics).  The stacked / transposed weights
+        are kept between forwards (op.conv.weight_derived)."""
         from op import conv as conv_op
         B, C, H, W = h.shape
         s = float(int(C) ** (-0.5))
         fold = math.frexp(s)[0] == 0.5  # s is a power of two
         sq = s if fold else 1.0
-        wqkv = torch.cat([self.NIN_0.W.t() * sq, self.NIN_1.W.t(), self.NIN_2.W.t()], 0)
-        bqkv = torch.cat([self.NIN_0.b * sq, self.NIN_1.b, self.NIN_2.b], 0)
+        n0, n1, n2, n3 = self.NIN_0, self.NIN_1, self.NIN_2, self.NIN_3
+        wqkv = conv_op.weight_derived(
+            self, "wqkv", [n0.W, n1.W, n2.W],
+            lambda: torch.cat([n0.W.t() * sq, n1.W.t(), n2.W.t()], 0))
+        bqkv = conv_op.weight_derived(
+            self, "bqkv", [n0.b, n1.b, n2.b], lambda: torch.cat([n0.b * sq, n1.b, n2.b], 0))
+        w3 = conv_op.weight_derived(self, "w3", [n3.W], lambda: n3.W.t().contiguous())
         qkv = conv_op.conv1x1(h, wqkv, bqkv).reshape(B, 3, C, H * W)
         from op import attention as attn_op
         if _ATTN_FUSED and attn_op.supported(qkv):
             out = attn_op.attention(qkv, 1.0 if fold else s).reshape(B, C, H, W)
-            return conv_op.conv1x1(out, self.NIN_3.W.t(), self.NIN_3.b)
-        q, k, v = qkv[:, 0], qkv[:, 1], qkv[:, 2]
-        w = torch.bmm(q.transpose(1, 2), k)
-        if not fold:
-            w = w * s
-        w = torch.softmax(w, dim=-1)
-        out = torch.bmm(v, w.transpose(1, 2)).reshape(B, C, H, W)
-        return conv_op.conv1x1(out, self.NIN_3.W.t(), self.NIN_3.b)
+        else:
+            q, k, v = qkv[:, 0], qkv[:, 1], qkv[:, 2]
+            w = torch.bmm(q.transpose(1, 2), k)
+            if not fold:
+                w = w * s
+            w = torch.softmax(w, dim=-1)
+            out = torch.bmm(v, w.transpose(1, 2)).reshape(B, C, H, W)
+        if skip is None:
+            return conv_op.conv1x1(out, w3, n3.b)
+        if _GEMM_TAIL:
+            return conv_op.conv1x1(out, w3, n3.b, skip=skip, div=div, stats=layers._GN_STATS)
+        return residual_rescale(skip, conv_op.conv1x1(out, w3, n3.b), None, div)
 
 
 class Upsample(nn.Module):
@@ -205,9 +230,7 @@ class ResnetBlockDDPMpp(nn.Module):
     def forward(self, x, temb=None):
         h, x = layers.gn_act_fanout(x, self.GroupNorm_0, self.act)
         h = conv_nobias(h, self.Conv_0)
-        bias_nc = self.Conv_0.bias[None, :].expand(x.shape[0], -1)
-        if temb is not None:
-            bias_nc = bias_nc + layers.temb_proj(self.Dense_0, self.act, temb)
+        bias_nc = layers.conv_temb_bias(self, self.act, temb, x.shape[0])
         h = gn_act(h, self.GroupNorm_1, self.act, bias_nc)
         h = self.Dropout_0(h)
         if x.shape[1] != self.out_ch:
@@ -251,6 +274,11 @@ class ResnetBlockBigGANpp(nn.Module):
                     else up_or_down_sampling.naive_downsample_2d(t, factor=2))
         return t
 
+    def _bias12(self):
+        """Conv_1.bias + Conv_2.bias (inference: kept between forwards)"""
+        b1, b2 = self.Conv_1.bias, self.Conv_2.bias
+        return conv_op.weight_derived(self, "bias12", [b1, b2], lambda: b1 + b2)
+
     def forward_pair(self, x1, x2, temb=None):
         """forward(torch.cat([x1, x2], 1), temb) -- the up path's skip concatenation -- at
         inference without building the concatenation: GroupNorm_0 from the parts' partial
@@ -275,10 +303,8 @@ class ResnetBlockBigGANpp(nn.Module):
         ss = group_norm_affine_partials(p1, x1.shape[0], C, self.GroupNorm_0, part2=p2)
         h = conv_op.conv3x3_pair(x1, x2, self.Conv_0.weight, pre=ss,
                                  stats=layers._GN_STATS)
-        bias_nc = self.Conv_0.bias[None, :].expand(h.shape[0], -1)
-        if temb is not None:
-            bias_nc = bias_nc + layers.temb_proj(self.Dense_0, self.act, temb)
-        bias = self.Conv_1.bias + self.Conv_2.bias
+        bias_nc = layers.conv_temb_bias(self, self.act, temb, h.shape[0])
+        bias = self._bias12()
         x = conv_op.conv1x1(x1, self.Conv_2.weight, None, x2)
         div = np.sqrt(2.) if self.skip_rescale else 1.0
         out = layers.gn_silu_conv(h, self.GroupNorm_1, self.Conv_1, bias_nc, bias, x, div)
@@ -305,20 +331,41 @@ class ResnetBlockBigGANpp(nn.Module):
                 link = None
             else:
                 h, x = r
+        projected = False
         if h is None:
-            h, x = layers.gn_act_fanout(x, self.GroupNorm_0, self.act)
-            h = self._resample(h)
-            x = self._resample(x)
-            h = conv_nobias(h, self.Conv_0)
-        bias_nc = self.Conv_0.bias[None, :].expand(h.shape[0], -1)
-        if temb is not None:
-            bias_nc = bias_nc + layers.temb_proj(self.Dense_0, self.act, temb)
+            if (fused and _FIR_PRE and self.fir and (self.up or self.down)
+                    and up_or_down_sampling.resample_2d_pre_supported(x, self.fir_kernel,
+                                                                      self.up)):
+                # inference: GroupNorm_0 + SiLU inside the FIR resampler's loads (the table from
+                # the input's partial statistics when its producer wrote them), no activated
+                # tensor written and read back
+                ss = layers.group_norm_affine(x, self.GroupNorm_0)
+                h = up_or_down_sampling.resample_2d_pre(x, ss, self.fir_kernel, self.up)
+            else:
+                h, x = layers.gn_act_fanout(x, self.GroupNorm_0, self.act)
+                h = self._resample(h)
+            if fused and self.up and _UP_SKIP_FIRST and x.is_cuda:
+                # inference: the 1x1 projection mixes channels, the FIR upsample acts per
+                # channel -- they commute, and projecting first runs the GEMM on a quarter of
+                # the pixels (down blocks project at the low resolution already)
+                x = self._resample(conv_nobias(x, self.Conv_2))
+                projected = True
+            else:
+                x = self._resample(x)
+            if (fused and _RESAMPLE_STATS and layers._GN_STATS
+                    and layers._wino_eligible(h, self.Conv_0)):
+                # GroupNorm_1's statistics from Conv_0's epilogue
+                h = conv_op.conv3x3(h, self.Conv_0.weight, None, stats=True)
+            else:
+                h = conv_nobias(h, self.Conv_0)
+        bias_nc = layers.conv_temb_bias(self, self.act, temb, h.shape[0])
         bias = self.Conv_1.bias
         if self.in_ch != self.out_ch or self.up or self.down:
             # the 1x1 skip conv's bias joins Conv_1's in the fused residual (no separate
             # full-tensor bias add after the GEMM)
-            x = conv_nobias(x, self.Conv_2)
-            bias = bias + self.Conv_2.bias
+            if not projected:
+                x = conv_nobias(x, self.Conv_2)
+            bias = self._bias12() if fused else bias + self.Conv_2.bias
         div = np.sqrt(2.) if self.skip_rescale else 1.0
         if fused:
             # GroupNorm_1 (+ time bias) + SiLU + Conv_1 + residual tail: two launches

@@ -217,9 +217,16 @@ class NCSNpp(nn.Module):
         if temb is not None and _TEMB_BANK and x.is_cuda and (
                 layers._TEMB_BANK_AD or layers.fused_inference_ok(self, x, self.act)):
             if self._denses is None:
-                self._denses = [m.Dense_0 for m in self.all_modules
-                                if hasattr(m, "Dense_0") and isinstance(m.Dense_0, nn.Linear)]
-            temb = layers.TembBank(temb, self.act, self._denses)
+                blocks = [m for m in self.all_modules
+                          if hasattr(m, "Dense_0") and isinstance(m.Dense_0, nn.Linear)]
+                self._denses = [m.Dense_0 for m in blocks]
+                self._conv0_biases = [m.Conv_0.bias for m in blocks]
+            if layers._TEMB_FOLD and layers.fused_inference_ok(self, x, self.act):
+                # inference: the bank's weights kept between forwards, Conv_0.bias folded in
+                temb = layers.TembBank(temb, self.act, self._denses, owner=self,
+                                       conv_biases=self._conv0_biases)
+            else:
+                temb = layers.TembBank(temb, self.act, self._denses)
         if not self.config.data.centered:
             x = 2 * x - 1.
         pyramid = x if self.progressive_input != "none" else None

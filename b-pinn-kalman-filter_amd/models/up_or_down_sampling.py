@@ -150,3 +150,30 @@ def downsample_2d(x, k=None, factor=2, gain=1):
     kt = fir_kernel(kk, gain, x.device, x.dtype)
     p = kt.shape[0] - factor
     return upfirdn2d(x, kt, down=factor, pad=((p + 1) // 2, p // 2))
+
+
+def _fir_args(x, k, up, factor):
+    kk = [1] * factor if k is None else k
+    kt = fir_kernel(kk, factor ** 2 if up else 1, x.device, x.dtype)
+    p = kt.shape[0] - factor
+    pad = ((p + 1) // 2 + factor - 1, p // 2) if up else ((p + 1) // 2, p // 2)
+    return kt, (factor if up else 1), (1 if up else factor), pad
+
+
+def resample_2d_pre_supported(x, k=None, up=True, factor=2):
+    """resample_2d_pre has a kernel form for x (op.upfirdn2d.upfirdn2d_pre_supported)."""
+    from op.upfirdn2d import lib
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0):
+        return False
+    kt, u, d, pad = _fir_args(x, k, up, factor)
+    return bool(lib.bpk_upfirdn2d_pre_supported(x.shape[0] * x.shape[1], x.shape[2], x.shape[3],
+                                                kt.shape[0], kt.shape[1], u, d, pad[0], pad[1]))
+
+
+def resample_2d_pre(x, pre, k=None, up=True, factor=2):
+    """upsample_2d (up) / downsample_2d of silu(x * s + t), pre[n, c] = (s, t): GroupNorm +
+    SiLU inside the FIR resampler's loads (inference; see resample_2d_pre_supported)."""
+    from op.upfirdn2d import upfirdn2d_pre
+    kt, u, d, pad = _fir_args(x, k, up, factor)
+    return upfirdn2d_pre(x, pre, kt, up=u, down=d, pad=pad)

@@ -93,11 +93,54 @@ def _transform_into(weight, U, ft, form=16):
 
 
 def refresh_filters(registry: list):
-    """Recompute, in place, the registered transforms whose weight changed since capture."""
+    """Recompute, in place, the registered transforms (and weight-derived tensors, see
+    weight_derived) whose weight changed since capture."""
     for i, (weight, U, ft, ver, form) in enumerate(registry):
+        if form == "derived":  # (params, out, build, versions, "derived")
+            now = tuple(p._version for p in weight)
+            if now != ver:
+                with torch.no_grad():
+                    U.copy_(ft())
+                registry[i] = (weight, U, ft, now, form)
+            continue
         if weight._version != ver:
             _transform_into(weight, U, ft, form)
             registry[i] = (weight, U, ft, weight._version, form)
+
+
+# BPK_WEIGHT_CACHE=0: weight-only tensors are rebuilt by every forward; read once at import
+_WEIGHT_CACHE = os.environ.get("BPK_WEIGHT_CACHE", "1") == "1"
+
+
+def weight_derived(owner, key, params, build):
+    """build() -- a tensor computed from the parameters `params` alone (stacked or transposed
+    weights, summed biases) -- kept on the module `owner` under `key` while every parameter's
+    version counter, storage and device are unchanged, so an inference forward does not launch
+    the kernels that rebuild it.  An optimizer step, load_state_dict, EMA copy_to or any other
+    in-place write moves a version counter and the next call rebuilds.  Under autograd (a
+    parameter requires grad with grad mode on) nothing is cached: the graph must see build().
+    Under hipGraph capture the rules are filter_transform's: build() is recorded and the cache
+    left alone, unless the capture runs inside static_filters and an eager call has filled the
+    cache -- then the cached tensor is read and registered for refresh_filters."""
+    if not _WEIGHT_CACHE or (torch.is_grad_enabled() and any(p.requires_grad for p in params)):
+        return build()
+    sig = tuple((p._version, p.data_ptr(), p.device) for p in params)
+    store = owner.__dict__.setdefault("_bpk_wcache", {})
+    hit = store.get(key)
+    valid = hit is not None and hit[0] == sig
+    if params[0].is_cuda and torch.cuda.is_current_stream_capturing():
+        if _STATIC_FILTERS is None or not valid:
+            return build()
+        if not any(e[1] is hit[1] for e in _STATIC_FILTERS):
+            _STATIC_FILTERS.append((tuple(params), hit[1], build,
+                                    tuple(p._version for p in params), "derived"))
+        return hit[1]
+    if valid:
+        return hit[1]
+    with torch.no_grad():
+        out = build().detach()
+    store[key] = (sig, out)
+    return out
 
 
 _FILTER_BATCH = None  # {(weight data_ptr, ft): (shape, U)} while a FilterBatch is active
@@ -1403,13 +1446,17 @@ def _gemm_nchw(w, ldw, x, K1, x2, K2, b, y, N, M, P):
                                        stream_ptr(x.device)), "conv1x1")
 
 
-def conv1x1(x, weight, bias=None, x2=None):
+def conv1x1(x, weight, bias=None, x2=None, skip=None, div=1.0, stats=False):
     """1x1 conv of NCHW x (or of the channel concatenation [x, x2], without building it)
-    with weight [Cout, Cin(, 1, 1)] (+ bias): the MFMA GEMM kernel.  Inference only."""
-    require_hip(x, weight, bias, x2, what="conv1x1")
+    with weight [Cout, Cin(, 1, 1)] (+ bias): the MFMA GEMM kernel.  Inference only.
+    With `skip` the store is the residual tail (skip + (conv + bias)) / div, bit-identical to
+    residual_rescale(skip, conv1x1(...), None, div); stats=True attaches the GroupNorm partial
+    statistics of the stored values (gn_partials: the layout of ensure_gn_partials), both from
+    the GEMM's own store (bpk_gemm_nchw_ex_f32)."""
+    require_hip(x, weight, bias, x2, skip, what="conv1x1")
     if not gemm1x1_supported(x, weight, x2):
         raise RuntimeError(f"conv1x1: unsupported shape {tuple(x.shape)} x {tuple(weight.shape)}")
-    _inference_only(x, weight, bias, x2)
+    _inference_only(x, weight, bias, x2, skip)
     x = x.contiguous()
     x2 = None if x2 is None else x2.contiguous()
     N, K1, H, W = x.shape
@@ -1418,7 +1465,24 @@ def conv1x1(x, weight, bias=None, x2=None):
     w = weight.detach().reshape(M, K1 + K2).contiguous()
     b = None if bias is None else bias.detach().contiguous()
     y = torch.empty((N, M, H, W), dtype=torch.float32, device=x.device)
-    _gemm_nchw(w, K1 + K2, x, K1, x2, K2, b, y, N, M, H * W)
+    if skip is None and not stats:
+        _gemm_nchw(w, K1 + K2, x, K1, x2, K2, b, y, N, M, H * W)
+    else:
+        P = H * W
+        sk = None if skip is None else skip.detach().contiguous()
+        if sk is not None and (sk.shape != y.shape or sk.dtype != torch.float32):
+            raise RuntimeError(f"conv1x1: skip {tuple(sk.shape)} != output {tuple(y.shape)}")
+        R = P // GN_PART_COUNT  # P % 128 == 0 (gemm1x1_supported)
+        part = torch.empty((N, M, R, 2), dtype=torch.float32, device=x.device) if stats else None
+        nws = lib.bpk_gemm_nchw_splitk_bytes(N, M, P, K1, K2)
+        ws = torch.empty(nws // 4, dtype=torch.float32, device=x.device) if nws > 0 else None
+        check(lib.bpk_gemm_nchw_ex_f32(
+            w.data_ptr(), K1 + K2, x.data_ptr(), K1, None if x2 is None else x2.data_ptr(), K2,
+            None if b is None else b.data_ptr(), None if sk is None else sk.data_ptr(),
+            float(div), y.data_ptr(), None if part is None else part.data_ptr(),
+            None if ws is None else ws.data_ptr(), N, M, P, stream_ptr(x.device)), "conv1x1_ex")
+        if part is not None:
+            attach_gn_partials(y, part, R)
     flops.add("gemm1x1", 2.0 * N * M * (K1 + K2) * H * W)
     return y
 

@@ -48,6 +48,42 @@ def upfirdn2d_raw(x: torch.Tensor, kernel: torch.Tensor, up=(1, 1), down=(1, 1),
     return out
 
 
+def upfirdn2d_pre_supported(x, kernel, pre, up=1, down=1, pad=(0, 0)) -> bool:
+    """upfirdn2d_pre has a kernel form for these operands (else: materialise the activation and
+    call upfirdn2d)."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and torch.is_tensor(kernel) and kernel.dim() == 2 and torch.is_tensor(pre)
+            and pre.dtype == torch.float32 and tuple(pre.shape) == (x.shape[0], x.shape[1], 2)):
+        return False
+    n, c, in_h, in_w = x.shape
+    return bool(lib.bpk_upfirdn2d_pre_supported(n * c, in_h, in_w, kernel.shape[0],
+                                                kernel.shape[1], up, down, pad[0], pad[1]))
+
+
+def upfirdn2d_pre(x, pre, kernel, up=1, down=1, pad=(0, 0)):
+    """upfirdn2d(silu(x * s + t), kernel, up, down, pad) with pre[n, c] = (s, t) (the table of
+    op.norm_act.group_norm_affine*): GroupNorm + SiLU applied inside the resampler's loads, the
+    padding zero after the activation.  Inference only; the forms of upfirdn2d_pre_supported."""
+    require_hip(x, pre, kernel, what="upfirdn2d_pre")
+    if torch.is_grad_enabled() and (x.requires_grad or pre.requires_grad):
+        raise RuntimeError("upfirdn2d_pre is inference-only")
+    if not upfirdn2d_pre_supported(x, kernel, pre, up, down, pad):
+        raise RuntimeError(f"upfirdn2d_pre: no kernel form for {tuple(x.shape)} taps "
+                           f"{tuple(kernel.shape)} up {up} down {down} pad {tuple(pad)}")
+    x = x.contiguous()
+    pre = pre.contiguous()
+    kernel = kernel.to(device=x.device, dtype=torch.float32).contiguous()
+    n, c, in_h, in_w = x.shape
+    kh, kw = kernel.shape
+    out_h, out_w = _out_size(in_h, in_w, kh, kw, (up, up), (down, down),
+                             (pad[0], pad[1], pad[0], pad[1]))
+    out = torch.empty((n, c, out_h, out_w), device=x.device, dtype=x.dtype)
+    check(lib.bpk_upfirdn2d_pre_f32(x.data_ptr(), pre.data_ptr(), kernel.data_ptr(),
+                                    out.data_ptr(), n * c, in_h, in_w, kh, kw, up, down, pad[0],
+                                    pad[1], out_h, out_w, stream_ptr(x.device)), "upfirdn2d_pre")
+    return out
+
+
 def _adjoint_pad(in_h, in_w, kh, kw, up, down, pad, out_h, out_w):
     up_x, up_y = up
     down_x, down_y = down

@@ -63,6 +63,19 @@ int bpk_upfirdn2d_f64(const double* x, const double* kernel, double* out, int ma
                       int in_w, int minor, int kernel_h, int kernel_w, int up_x, int up_y,
                       int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                       int out_h, int out_w, void* stream);
+/* upfirdn2d of silu(x * s + t) with (s, t) = pre[plane] -- GroupNorm + SiLU applied while
+ * loading (pre [major, 2] = the [N, C, 2] table of bpk_group_norm_affine*_f32), so a resample
+ * block's activated tensor is never written: x [major, in_h, in_w] (NCHW planes), the same
+ * (up, down, pad0, pad1) on both axes.  Taps that fall outside the plane contribute 0: the
+ * padding is zero AFTER the activation, not silu(t).  supported(): the forms the NCSN++
+ * resample blocks use -- up 2 / pad0 2 with out_w % 4 == 0, down 2 / pad0 1 -- taps <= 4x4,
+ * in_w % 4 == 0; x and out 16-byte aligned.  Anything else: the plain entry on a
+ * materialised activation. */
+int bpk_upfirdn2d_pre_supported(int major, int in_h, int in_w, int kernel_h, int kernel_w, int up,
+                                int down, int pad0, int pad1);
+int bpk_upfirdn2d_pre_f32(const float* x, const float* pre, const float* kernel, float* out,
+                          int major, int in_h, int in_w, int kernel_h, int kernel_w, int up,
+                          int down, int pad0, int pad1, int out_h, int out_w, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * fused_bias_act: out = scale * act(x + bias[(i / step_b) % size_b]), act in
@@ -577,6 +590,19 @@ int64_t bpk_gemm_nchw_splitk_bytes(int N, int M, int P, int K1, int K2);
 int bpk_gemm_nchw_splitk_f32(const float* W, int ldw, const float* X1, int K1, const float* X2,
                              int K2, const float* bias, float* Y, float* workspace, int N, int M,
                              int P, void* stream);
+/* The same GEMM with the residual-block tail and GroupNorm partial statistics in its store
+ * (the attention blocks' NIN_3 at inference):
+ *   Y = (skip + (W [X1; X2] + bias)) / div      skip [N, M, P] (NULL: Y = W [X1; X2] + bias)
+ * in the operation order and with the correctly rounded division of bpk_residual_rescale_f32,
+ * so Y is bit-identical to bpk_gemm_nchw_splitk_f32 followed by it.  stats (NULL: none)
+ * [N, M, P / 128, 2] receives (mean, M2) of every 128 consecutive stored pixels of a row --
+ * the records of bpk_group_norm_chunk_partials_f32, read by
+ * bpk_group_norm_affine_partials_f32(part, R = P / 128, count = 128, ...) -- reduced in a
+ * fixed order without atomics.  workspace: bpk_gemm_nchw_splitk_bytes() bytes (NULL: no split;
+ * under split-K the tail and the statistics run in the reduce launch). */
+int bpk_gemm_nchw_ex_f32(const float* W, int ldw, const float* X1, int K1, const float* X2, int K2,
+                         const float* bias, const float* skip, float div, float* Y, float* stats,
+                         float* workspace, int N, int M, int P, void* stream);
 /* Strided batched GEMM on the f32 MFMA: C(b, m, n) = alpha * sum_k A(b, m, k) B(b, k, n)
  * (+ bias[n] for bias_mode 1, bias[m] for 2; accumulate != 0: C += instead of C =), each operand
  * addressed by element strides (A(b, m, k) = A[b sab + m sam + k sak], ...), so transposes
