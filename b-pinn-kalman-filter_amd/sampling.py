@@ -24,7 +24,11 @@ Execution (the MI355X part):
   * batch-sharded multi-GPU: each rank owns samples [r*B, (r+1)*B); the only
     exchange is a 2-float all-reduce per Langevin step (the batch-mean norms of
     sampling.py:276-277); noise is Philox keyed by the global sample index, so
-    results do not depend on the number of ranks.
+    results do not depend on the number of ranks;
+  * conditional sampling (`PCEngine(condition="inpaint" | "colorize")`, public API in
+    controllable_generation.py): the reference's data-consistency projection after every
+    corrector and predictor half-step sits in the update kernels' store, so the conditioned
+    step is the same launch sequence and the same single graph.
 User-registered predictors/correctors fall back to the reference-style loop.
 """
 from __future__ import annotations
@@ -407,6 +411,25 @@ def pc_timesteps(sde, eps):
     return torch.linspace(sde.T, eps, sde.N)
 
 
+def marginal_rows(sde, t):
+    """[len(t), 2] float32 (mean coefficient, std) of sde.marginal_prob at t: the scalars of
+    the conditional samplers' projection (reference controllable_generation.py:48, :140).
+    The mean coefficient is marginal_prob's mean of a unit input, so a user SDE with a linear
+    mean needs nothing beyond the reference's interface."""
+    t = t.to(torch.float32)
+    mean, std = sde.marginal_prob(torch.ones((t.shape[0], 1, 1, 1), dtype=torch.float32,
+                                             device=t.device), t)
+    return torch.stack([mean.reshape(-1).to(torch.float32), std.to(torch.float32)], dim=1)
+
+
+_CONDITIONS = {None: K.COND_NONE, "inpaint": K.COND_INPAINT, "colorize": K.COND_COLORIZE}
+
+
+def decouple(x, M):
+    """Reference controllable_generation.py:114-115 (couple: the same with inverse(M))."""
+    return torch.einsum('bihw,ij->bjhw', x, M.to(x.device))
+
+
 def _graph_collective(ctx) -> bool:
     """Capture the sharded PC step's RCCL all-reduce inside the step graph (opt-in,
     BPK_PC_GRAPH_ALLREDUCE=1): one graph replay per step instead of segments with a
@@ -427,7 +450,11 @@ class PCEngine:
 
     def __init__(self, sde, shape, predictor, corrector, snr, n_steps=1, continuous=False,
                  denoise=True, eps=1e-3, device="cuda", seed=None, use_graph=True, dist_ctx=None,
-                 noise_fn=None):
+                 noise_fn=None, condition=None):
+        if condition not in _CONDITIONS:
+            raise ValueError(f"condition must be None, 'inpaint' or 'colorize', got {condition!r}")
+        if condition == "colorize" and tuple(shape)[1] != 3:
+            raise ValueError(f"colorization needs 3 channels, got shape {tuple(shape)}")
         if not self.supports(sde, predictor, corrector, False):
             raise NotImplementedError(
                 f"PCEngine has no fused step for {sde.__class__.__name__} with "
@@ -458,6 +485,8 @@ class PCEngine:
         self._graph_key = None
         self.pred_kind = self._pred_kind()
         self.corr_mode = {LangevinCorrector: 0, AnnealedLangevinDynamics: 1}.get(corrector, None)
+        self.condition = condition
+        self.cond = _CONDITIONS[condition]
         self._build_tables()
 
     # which built-in kernels apply
@@ -501,6 +530,28 @@ class PCEngine:
         self.labels = torch.empty(self.B, dtype=torch.float32, device=self.device)
         self.red = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.ws = K.langevin_workspace(self.B, self.D, self.device)
+        if self.cond != K.COND_NONE:
+            # static buffers of the projection: the graph reads them, reset() rewrites them
+            self.mtab = torch.stack([marginal_rows(sde, torch.ones(1) * ts[i])
+                                     for i in range(sde.N)]).to(self.device)  # [N, 1, 2]
+            self.cdata = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+            self.cmask = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+            self.mats = K.color_mats() if self.cond == K.COND_COLORIZE else None
+
+    def _cond_kw(self, i, draw):
+        """Keywords that put the projection into an update kernel's store (none when
+        unconditioned); the data draw of the update with draw id `draw`."""
+        if self.cond == K.COND_NONE:
+            return {}
+        return dict(cond=self.cond, data=self.cdata, mask=self.cmask, mtab=self.mtab,
+                    mats=self.mats,
+                    noise2=self._noise(i, K.DATA_DRAW + draw) if i is not None else None)
+
+    def _project(self, x, x_mean, i, draw):
+        """A None half-step of a conditioned run: (x, x) projected with fresh data noise."""
+        kw = self._cond_kw(i, draw)
+        K.project(kw.pop("cond"), x, kw.pop("mtab"), self.step, x_out=x, x_mean=x_mean,
+                  seed=self.seed, draw=draw, sample_offset=self.sample_offset, **kw)
 
     def _noise(self, i, draw):
         if self.noise_fn is None:
@@ -525,16 +576,22 @@ class PCEngine:
                                      sample_offset=self.sample_offset)
                     if self.world > 1:
                         yield "all_reduce"  # red <- sum over ranks
+                # the reference projects once per corrector call, after its last Langevin step
+                ckw = self._cond_kw(i, 1 + j) if j == self.n_steps - 1 else {}
                 K.langevin_update(self.corr_mode, x, m, self.coef, self.step, self.red, x_out=x,
                                   x_mean=x_mean, noise=nz, B_global=self.B_global, score_mode=mode,
                                   snr=self.snr, seed=self.seed, draw=1 + j,
-                                  sample_offset=self.sample_offset)
+                                  sample_offset=self.sample_offset, **ckw)
+        elif self.cond != K.COND_NONE:
+            self._project(x, x_mean, i, 1)
         if self.pred_kind is not None:
             m = model(x, labels).contiguous()
             nz = self._noise(i, 0) if i is not None else None
             K.predictor(self.pred_kind, x, m, self.coef, self.step, x_out=x, x_mean=x_mean,
                         noise=nz, score_mode=mode, drift_mul_x=int(sde_vp_like), seed=self.seed,
-                        draw=0, sample_offset=self.sample_offset)
+                        draw=0, sample_offset=self.sample_offset, **self._cond_kw(i, 0))
+        elif self.cond != K.COND_NONE:
+            self._project(x, x_mean, i, 0)
         elif self.corr_mode is not None:
             # NonePredictor returns (x, x): the step's x_mean is the corrector's noisy x, not
             # its x_mean (reference sampling.py:249-250, :405-406)
@@ -555,10 +612,39 @@ class PCEngine:
         x = x_init.to(self.device, torch.float32).contiguous().clone()
         return x, x.clone()
 
+    def _set_condition(self, x, data, mask):
+        """Load data / mask into the static buffers and turn the prior x into the reference's
+        initial state (controllable_generation.py:73, :168-172); once per run, torch ops."""
+        if data is None:
+            raise ValueError(f"PCEngine(condition={self.condition!r}).reset needs data=")
+        for name, t in (("data", data), ("mask", mask)):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError(f"PCEngine.reset: {name} must be a HIP (cuda) tensor, got "
+                                   f"device {t.device}")
+        self.cdata.copy_(data.to(torch.float32))
+        if self.cond == K.COND_INPAINT:
+            if mask is None:
+                raise ValueError("PCEngine(condition='inpaint').reset needs mask=")
+            self.cmask.copy_(mask.to(torch.float32))
+            return self.cdata * self.cmask + x * (1. - self.cmask)
+        self.cmask.zero_()
+        self.cmask[:, :1] = 1.  # get_mask: channel 0 of the decoupled image is the known one
+        M, invM = self.mats
+        return decouple(decouple(self.cdata, M) * self.cmask + decouple(x * (1. - self.cmask), M),
+                        invM).contiguous()
+
     @torch.no_grad()
-    def reset(self, model, x_init=None):
-        """Draw / load the prior, (re)capture the step graph if needed, zero the step counter."""
+    def reset(self, model, x_init=None, data=None, mask=None):
+        """Draw / load the prior, (re)capture the step graph if needed, zero the step counter.
+        A conditioned engine takes the known image (`data`, the gray image for colorize) and,
+        for inpainting, the 0/1 `mask` of this rank's samples; x_init is then the prior the
+        initial state is built from.  New data / mask of the same shape reuse the graph."""
         x, x_mean = self.init_state(x_init)
+        if self.cond != K.COND_NONE:
+            x = self._set_condition(x, data, mask)
+            x_mean = x.clone()
+        elif data is not None or mask is not None:
+            raise ValueError("data= / mask= need PCEngine(condition=...)")
         self.step.zero_()
         if self.use_graph:
             key = (self.seed, id(model))
@@ -600,9 +686,9 @@ class PCEngine:
         return self._x, self._xm
 
     @torch.no_grad()
-    def run(self, model, x_init=None, n_iters=None, progress=None):
+    def run(self, model, x_init=None, n_iters=None, progress=None, data=None, mask=None):
         """Run n_iters (default N) PC steps from the prior; returns (x, x_mean)."""
-        self.reset(model, x_init)
+        self.reset(model, x_init, data=data, mask=mask)
         x, xm = self.advance(self.sde.N if n_iters is None else n_iters, progress)
         return x.clone(), xm.clone()
 
@@ -658,8 +744,8 @@ class PCEngine:
             self.capture_error = repr(e)
             torch.cuda.synchronize(self.device)
 
-    def __call__(self, model, inverse_scaler=lambda v: v, x_init=None):
-        x, x_mean = self.run(model, x_init)
+    def __call__(self, model, inverse_scaler=lambda v: v, x_init=None, data=None, mask=None):
+        x, x_mean = self.run(model, x_init, data=data, mask=mask)
         out = x_mean if self.denoise else x
         return inverse_scaler(out), self.sde.N * (self.n_steps + 1)
 

@@ -394,6 +394,55 @@ int bpk_langevin_update_f32(int mode, const float* x, const float* model_out, co
                             int B_global, int64_t sample_offset, const float* coef,
                             int coef_bdim, const int* step_ptr, int score_mode, float snr,
                             uint64_t seed, int draw, void* stream);
+/* Conditional PC sampling: the data-consistency projection of the reference's
+ * controllable_generation.py, applied to the updated x before the single store
+ * of x_out / x_mean.  (mc, sd) = mtab[*step_ptr][b] is sde.marginal_prob's mean
+ * coefficient and std, `mtab` [n_steps, mtab_bdim, 2] float32 built on the host,
+ * indexed by the same step counter as `coef` (mtab_bdim 1 or B).  z2 is a
+ * second N(0,1) draw: `noise2` [B, D] when non-NULL, else the Philox stream at
+ * the same global element index under draw id BPK_DATA_DRAW + draw.
+ *   BPK_COND_INPAINT (controllable_generation.py:44-52), per element, `data` and
+ *   `mask` (float32 0/1, 1 = known) [B, D]:
+ *     md_mean = mc * data;  md = md_mean + z2 * sd
+ *     x'      = xn * (1 - mask) + md * mask
+ *     x_mean' = x' * (1 - mask) + md_mean * mask        (from x', as the reference)
+ *   BPK_COND_COLORIZE (controllable_generation.py:105-119, :136-144), per pixel over
+ *   C == 3 channels, `data` = the gray image [B, 3, HW], mask not read:
+ *     u = decouple(xn), out_j = sum_i in_i * M[i][j];  u_0 = u_0 * 0 + (mc *
+ *     decouple(data)_0 + z2_0 * sd) * 1;  x' = couple(u) (with invM);
+ *     x_mean' = couple(v), v = decouple(x'), v_0 = v_0 * 0 + mc * decouple(data)_0
+ *   Only channel 0's elements of the data draw are consumed.  `mats` is HOST memory,
+ *   18 floats: M then invM = inverse(M), row major (NULL unless colorize).
+ * bpk_pc_project_f32 is the projection alone, for the half-steps whose update is
+ * None (the reference projects (x, x) there, controllable_generation.py:47, sampling.py
+ * :242-250, :322-330); the _cond_ forms are bpk_pc_predictor_f32 / bpk_langevin_update_f32
+ * with the projection in the store (cond BPK_COND_NONE = exactly those).  x_out may
+ * alias x. */
+#define BPK_DATA_DRAW 0x100
+enum {
+  BPK_COND_NONE = 0,
+  BPK_COND_INPAINT = 1,
+  BPK_COND_COLORIZE = 2,
+};
+int bpk_pc_project_f32(int cond, const float* x, const float* noise2, float* x_out, float* x_mean,
+                       const float* data, const float* mask, const float* mtab, int mtab_bdim,
+                       const float* mats, int B, int C, int64_t D, int64_t sample_offset,
+                       const int* step_ptr, uint64_t seed, int draw, void* stream);
+int bpk_pc_predictor_cond_f32(int cond, int kind, const float* x, const float* model_out,
+                              const float* noise, const float* noise2, float* x_out,
+                              float* x_mean, const float* data, const float* mask,
+                              const float* mtab, int mtab_bdim, const float* mats, int B, int C,
+                              int64_t D, int64_t sample_offset, const float* coef, int coef_bdim,
+                              const int* step_ptr, int score_mode, int drift_mul_x, uint64_t seed,
+                              int draw, void* stream);
+int bpk_langevin_update_cond_f32(int cond, int mode, const float* x, const float* model_out,
+                                 const float* noise, const float* noise2, const float* red,
+                                 float* x_out, float* x_mean, const float* data,
+                                 const float* mask, const float* mtab, int mtab_bdim,
+                                 const float* mats, int B, int C, int64_t D, int B_global,
+                                 int64_t sample_offset, const float* coef, int coef_bdim,
+                                 const int* step_ptr, int score_mode, float snr, uint64_t seed,
+                                 int draw, void* stream);
 /* step_ptr[0] += 1 (device-side step counter for graph replay) */
 int bpk_step_increment(int* step_ptr, void* stream);
 /* labels[b] = table[*step_ptr] for b < B (time conditioning for the score net) */
