@@ -14,6 +14,13 @@
 //             obs-dim rank-1 downdates of S- by the columns of U (= K S_z) with the row of S in
 //             64 registers and S_kk / x_k broadcast by v_readlane: no barrier and no LDS access
 //             inside the n x obs-dim chain.
+//   k_smooth  one backward (Rauch-Tung-Striebel) step: C = sum_s wc_s (X_s - m)(Y_s - m-)^T by
+//             the same tiled loop, then wave 0 does U = C S-^-T, y and m^s exactly as the update
+//             does (S_z := S-, z := m^s_+) while wave 1 solves S- B = S^s_+ (lane = column) in
+//             the tile the chunks left free; W = U B by all four waves (4 x 4 outputs per
+//             thread) overwrites S-; S is staged through the B tile and wave 0 runs n rank-1
+//             updates by W's columns, then n downdates by U's, on its 64-register row.  Three
+//             tiles, 49 920 B, as the update.
 //
 // LDS tiles are [64][65]: a column walk (lane = row, fixed column) and a row walk (lane =
 // column) both touch 32 distinct banks per half wave (65 mod 32 = 1).
@@ -215,36 +222,22 @@ __global__ __launch_bounds__(kThreads) void k_root(const float* __restrict__ pts
 }
 
 // ---------------------------------------------------------------------------------------
-constexpr int kChunk = 32;  // sigma points per P_xz tile
+constexpr int kChunk = 32;  // sigma points per cross-covariance tile
 
-__global__ __launch_bounds__(kThreads) void k_update(
-    const float* __restrict__ mean, const float* __restrict__ S, const float* __restrict__ xp,
-    const float* __restrict__ zp, const float* __restrict__ zmean, const float* __restrict__ Sz,
-    const float* __restrict__ obs, float* __restrict__ mean_out, float* __restrict__ tril_out,
-    int* __restrict__ status, int64_t N, int n, int dz, float wc0, float wi, int groups) {
-  __shared__ float T[kMaxDim * kLd];   // P_xz tiles (2 x 32 x 64), later S- / S+ staging
-  __shared__ float P[kMaxDim * kLd];   // P_xz, then U = P_xz S_z^-T in place
-  __shared__ float Zt[kMaxDim * kLd];  // S_z
-  const int64_t f = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const Rows rows(f, N, groups, n);
+// Shared by k_update and k_smooth, all 256 threads: P[i][j] = sum_s wc_s (X_s - mx)[i]
+// (Z_s - mz)[j] (P_xz of the update with Z = the measured points, C of the smoother with Z = the
+// propagated points), contraction in chunks of kChunk points staged in T (2 x 32 x 64 floats);
+// thread -> i = ti + 16 a, j = tj + 16 b.  mx / mz: this lane's element of the two means (0 past
+// the dimension).  Rows and columns past (n, dz) come out 0.  The caller synchronises before it
+// reads P or reuses T.
+__device__ __forceinline__ void cross_cov(float* T, float* P, const float* __restrict__ xp,
+                                          const float* __restrict__ zp, float mx, float mz,
+                                          const Rows& rows, int n, int dz, float wc0, float wi,
+                                          int tid) {
+  const int lane = tid & 63, w = tid >> 6;
   const int ns1 = 2 * n + 1;
   float* Xc = T;
   float* Zc = T + kChunk * kMaxDim;
-
-  for (int idx = tid; idx < kMaxDim * kLd; idx += kThreads) Zt[idx] = 0.f;
-  __syncthreads();
-  {
-    const float* Szf = Sz + f * dz * dz;
-    for (int idx = tid; idx < dz * dz; idx += kThreads) {
-      const int j = idx / dz, c = idx % dz;
-      if (c <= j) Zt[j * kLd + c] = Szf[idx];
-    }
-  }
-
-  // P_xz[i][j] = sum_s wc_s (X_s - m)[i] (Z_s - zhat)[j]; thread -> i = ti + 16 a, j = tj + 16 b
-  const float mx = lane < n ? mean[f * n + lane] : 0.f;
-  const float mz = lane < dz ? zmean[f * dz + lane] : 0.f;
   const int ti = tid >> 4, tj = tid & 15;
   float acc[4][4] = {};
   for (int s0 = 0; s0 < ns1; s0 += kChunk) {
@@ -279,6 +272,56 @@ __global__ __launch_bounds__(kThreads) void k_update(
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int b = 0; b < 4; ++b) P[(ti + 16 * a) * kLd + tj + 16 * b] = acc[a][b];
+}
+
+// Shared by k_update and k_smooth, wave 0 alone, lane = row: P := U = P Zt^-T in place by forward
+// substitution (rows are independent), y = Zt^-1 v (v = this lane's element of the innovation,
+// 0 past dz), and the return value mx + (U y)[lane].
+__device__ __forceinline__ float gain_mean(float* P, const float* Zt, float v, float mx, int dz,
+                                           int lane) {
+  for (int j = 0; j < dz; ++j) {
+    float a = P[lane * kLd + j];
+    for (int c = 0; c < j; ++c) a = fmaf(-P[lane * kLd + c], Zt[j * kLd + c], a);
+    P[lane * kLd + j] = a / Zt[j * kLd + j];
+  }
+  // Zt y = v; lane c ends up holding y_c
+  for (int c = 0; c < dz; ++c) {
+    const float yc = __shfl(v, c) / Zt[c * kLd + c];
+    if (lane > c) v = fmaf(-yc, Zt[lane * kLd + c], v);
+    if (lane == c) v = yc;
+  }
+  float mnew = mx;
+  for (int c = 0; c < dz; ++c) mnew = fmaf(P[lane * kLd + c], __shfl(v, c), mnew);
+  return mnew;
+}
+
+// Zt := the lower triangle of the d x d factor F, exact zeros everywhere else in the tile.
+__device__ __forceinline__ void stage_tril(float* Zt, const float* __restrict__ F, int d,
+                                           int tid) {
+  for (int idx = tid; idx < kMaxDim * kLd; idx += kThreads) Zt[idx] = 0.f;
+  __syncthreads();
+  for (int idx = tid; idx < d * d; idx += kThreads) {
+    const int j = idx / d, c = idx % d;
+    if (c <= j) Zt[j * kLd + c] = F[idx];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_update(
+    const float* __restrict__ mean, const float* __restrict__ S, const float* __restrict__ xp,
+    const float* __restrict__ zp, const float* __restrict__ zmean, const float* __restrict__ Sz,
+    const float* __restrict__ obs, float* __restrict__ mean_out, float* __restrict__ tril_out,
+    int* __restrict__ status, int64_t N, int n, int dz, float wc0, float wi, int groups) {
+  __shared__ float T[kMaxDim * kLd];   // P_xz tiles (2 x 32 x 64), later S- / S+ staging
+  __shared__ float P[kMaxDim * kLd];   // P_xz, then U = P_xz S_z^-T in place
+  __shared__ float Zt[kMaxDim * kLd];  // S_z
+  const int64_t f = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const Rows rows(f, N, groups, n);
+
+  stage_tril(Zt, Sz + f * dz * dz, dz, tid);
+  const float mx = lane < n ? mean[f * n + lane] : 0.f;
+  const float mz = lane < dz ? zmean[f * dz + lane] : 0.f;
+  cross_cov(T, P, xp, zp, mx, mz, rows, n, dz, wc0, wi, tid);
   __syncthreads();  // tiles consumed: T becomes the staging tile of S-
   {
     const float* Sf = S + f * n * n;
@@ -287,21 +330,7 @@ __global__ __launch_bounds__(kThreads) void k_update(
   __syncthreads();
 
   if (w == 0) {
-    // U S_z^T = P_xz, row `lane` of U by forward substitution (rows are independent)
-    for (int j = 0; j < dz; ++j) {
-      float a = P[lane * kLd + j];
-      for (int c = 0; c < j; ++c) a = fmaf(-P[lane * kLd + c], Zt[j * kLd + c], a);
-      P[lane * kLd + j] = a / Zt[j * kLd + j];
-    }
-    // S_z y = z - zhat; lane c ends up holding y_c
-    float v = lane < dz ? obs[f * dz + lane] - mz : 0.f;
-    for (int c = 0; c < dz; ++c) {
-      const float yc = __shfl(v, c) / Zt[c * kLd + c];
-      if (lane > c) v = fmaf(-yc, Zt[lane * kLd + c], v);
-      if (lane == c) v = yc;
-    }
-    float mnew = mx;
-    for (int c = 0; c < dz; ++c) mnew = fmaf(P[lane * kLd + c], __shfl(v, c), mnew);
+    const float mnew = gain_mean(P, Zt, lane < dz ? obs[f * dz + lane] - mz : 0.f, mx, dz, lane);
     if (lane < n) mean_out[f * n + lane] = mnew;
 
     float row[kMaxDim];
@@ -310,6 +339,94 @@ __global__ __launch_bounds__(kThreads) void k_update(
       row[k] = (lane < n && k <= lane && k < n) ? T[lane * kLd + k] : 0.f;
     int flag = 0;
     for (int c = 0; c < dz; ++c) {
+      const float x = lane < n ? P[lane * kLd + c] : 0.f;
+      chol_rank1<-1>(row, x, n, lane, flag);
+    }
+#pragma unroll
+    for (int k = 0; k < kMaxDim; ++k) T[lane * kLd + k] = row[k];
+    if (lane == 0) status[f] = flag;
+  }
+  __syncthreads();
+  float* So = tril_out + f * n * n;
+  for (int idx = tid; idx < n * n; idx += kThreads) So[idx] = T[(idx / n) * kLd + idx % n];
+}
+
+// ---------------------------------------------------------------------------------------
+// One backward (Rauch-Tung-Striebel) step of the unscented smoother, see include/bpk.h.
+__global__ __launch_bounds__(kThreads) void k_smooth(
+    const float* __restrict__ mean, const float* __restrict__ S, const float* __restrict__ xp,
+    const float* __restrict__ yp, const float* __restrict__ pmean, const float* __restrict__ Sp,
+    const float* __restrict__ nmean, const float* __restrict__ Sn, float* __restrict__ mean_out,
+    float* __restrict__ tril_out, int* __restrict__ status, int64_t N, int n, float wc0, float wi,
+    int groups) {
+  __shared__ float T[kMaxDim * kLd];   // C tiles, then S^s_+ -> B = S-^-1 S^s_+, then S / S^s
+  __shared__ float P[kMaxDim * kLd];   // C, then U = C S-^-T in place
+  __shared__ float Zt[kMaxDim * kLd];  // S- (the prediction's factor), then W = U B
+  const int64_t f = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const Rows rows(f, N, groups, n);
+
+  stage_tril(Zt, Sp + f * n * n, n, tid);
+  const float mx = lane < n ? mean[f * n + lane] : 0.f;
+  const float mp = lane < n ? pmean[f * n + lane] : 0.f;
+  cross_cov(T, P, xp, yp, mx, mp, rows, n, n, wc0, wi, tid);
+  __syncthreads();  // tiles consumed: T becomes S^s_+ (zeros outside its lower triangle)
+  stage_tril(T, Sn + f * n * n, n, tid);
+  __syncthreads();
+
+  if (w == 0) {  // U, y and the smoothed mean, as the update does with S_z := S-, z := m^s_+
+    const float mnew = gain_mean(P, Zt, lane < n ? nmean[f * n + lane] - mp : 0.f, mx, n, lane);
+    if (lane < n) mean_out[f * n + lane] = mnew;
+  } else if (w == 1) {
+    // S- B = S^s_+ in place, lane = column: B[j][c] for j >= c (the zeros above the diagonal of
+    // S^s_+ make the terms c' < c exact no-ops, so every lane runs the same trip counts)
+    for (int j = 0; j < n; ++j) {
+      float a = T[j * kLd + lane];
+      for (int c = 0; c < j; ++c) a = fmaf(-Zt[j * kLd + c], T[c * kLd + lane], a);
+      if (lane <= j) T[j * kLd + lane] = a / Zt[j * kLd + j];
+    }
+  }
+  __syncthreads();
+  {  // W = U B by all four waves into the tile of S- (read for the last time above)
+    const int ti = tid >> 4, tj = tid & 15;
+    float acc[4][4] = {};
+#pragma unroll 4
+    for (int k = 0; k < n; ++k) {
+      float ua[4], bb[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) ua[a] = P[(ti + 16 * a) * kLd + k];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) bb[b] = T[k * kLd + tj + 16 * b];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = fmaf(ua[a], bb[b], acc[a][b]);
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) Zt[(ti + 16 * a) * kLd + tj + 16 * b] = acc[a][b];
+  }
+  __syncthreads();  // B consumed: T becomes the staging tile of S
+  {
+    const float* Sf = S + f * n * n;
+    for (int idx = tid; idx < n * n; idx += kThreads) T[(idx / n) * kLd + idx % n] = Sf[idx];
+  }
+  __syncthreads();
+
+  if (w == 0) {
+    float row[kMaxDim];
+#pragma unroll
+    for (int k = 0; k < kMaxDim; ++k)
+      row[k] = (lane < n && k <= lane && k < n) ? T[lane * kLd + k] : 0.f;
+    int flag = 0;
+    // updates first: every intermediate then dominates P^s (downdates first would pass through
+    // the nearly singular P - C P-^-1 C^T when Q is small)
+    for (int c = 0; c < n; ++c) {
+      const float x = lane < n ? Zt[lane * kLd + c] : 0.f;
+      chol_rank1<1>(row, x, n, lane, flag);
+    }
+    for (int c = 0; c < n; ++c) {
       const float x = lane < n ? P[lane * kLd + c] : 0.f;
       chol_rank1<-1>(row, x, n, lane, flag);
     }
@@ -386,5 +503,31 @@ extern "C" int bpk_ukf_update_f32(const float* mean, const float* scale_tril,
                      scale_tril, x_points, z_points, z_mean, z_tril, obs, mean_out,
                      scale_tril_out, status, N, n, dz, wc0, wi, groups);
   BPK_LAUNCH_CHECK("ukf_update");
+  return BPK_OK;
+}
+
+extern "C" int bpk_ukf_smooth_f32(const float* mean, const float* scale_tril,
+                                  const float* x_points, const float* y_points,
+                                  const float* pred_mean, const float* pred_tril,
+                                  const float* next_mean, const float* next_tril,
+                                  float* mean_out, float* scale_tril_out, int* status, int64_t N,
+                                  int n, float wc0, float wi, int groups, void* stream) {
+  UKF_GEO_CHECK("ukf_smooth", "n", n);
+  UKF_PTR("ukf_smooth", mean);
+  UKF_PTR("ukf_smooth", scale_tril);
+  UKF_PTR("ukf_smooth", x_points);
+  UKF_PTR("ukf_smooth", y_points);
+  UKF_PTR("ukf_smooth", pred_mean);
+  UKF_PTR("ukf_smooth", pred_tril);
+  UKF_PTR("ukf_smooth", next_mean);
+  UKF_PTR("ukf_smooth", next_tril);
+  UKF_PTR("ukf_smooth", mean_out);
+  UKF_PTR("ukf_smooth", scale_tril_out);
+  UKF_PTR("ukf_smooth", status);
+  if (N == 0) return BPK_OK;
+  hipLaunchKernelGGL(k_smooth, dim3((unsigned)N), dim3(kThreads), 0, bpk::as_stream(stream), mean,
+                     scale_tril, x_points, y_points, pred_mean, pred_tril, next_mean, next_tril,
+                     mean_out, scale_tril_out, status, N, n, wc0, wi, groups);
+  BPK_LAUNCH_CHECK("ukf_smooth");
   return BPK_OK;
 }

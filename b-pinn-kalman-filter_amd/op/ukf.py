@@ -3,11 +3,14 @@
 The reference delegates its filter to `torchfilter` (pinn_kalman/ukf.py:4-23), which it does
 not pin and which is absent here; these ops implement the standard square-root UKF (Van der
 Merwe & Wan 2001) with Merwe scaled sigma points for N independent filters of state dimension
-n <= 64, float32, forward only:
+n <= 64, float32 -- the forward filter steps and the backward step of the unscented
+Rauch-Tung-Striebel smoother:
 
   sigma_points    X_0 = m, X_i = m + gamma S[:, i-1], X_{n+i} = m - gamma S[:, i-1]
   unscented_root  weighted mean and square-root covariance of propagated points + noise factor
   kalman_update   cross covariance, gain by triangular solves, mean update, rank-1 downdates
+  rts_smooth      state / propagated-state cross covariance, smoother gain by triangular
+                  solves, smoothed mean, rank-1 updates then downdates of the posterior factor
 
 Row layout.  Filters are rows i = g * (N / groups) + r.  Every sigma-point tensor is 2-D
 [groups * (2n+1) * N / groups, dim] with rows ordered (g, s, r) -- `point_rows` gives the
@@ -141,4 +144,43 @@ def kalman_update(mean, scale_tril, x_points, z_points, z_mean, z_tril, obs, wc0
                                  obs.data_ptr(), m1.data_ptr(), s1.data_ptr(), status.data_ptr(),
                                  N, n, dz, float(wc0), float(wi), int(groups),
                                  stream_ptr(mean.device)), what)
+    return m1, s1, status
+
+
+def rts_smooth(mean, scale_tril, x_points, y_points, pred_mean, pred_tril, next_mean, next_tril,
+               wc0, wi, groups=1):
+    """One backward step t+1 -> t of the unscented Rauch-Tung-Striebel smoother.  Posterior at t
+    (mean [N, n], scale_tril [N, n, n]), its sigma points x_points [(2n+1) N, n] and their
+    images y_points [(2n+1) N, n] under the dynamics, the prediction at t+1 (pred_mean [N, n],
+    pred_tril [N, n, n]: `unscented_root` of y_points) and the smoothed belief at t+1
+    (next_mean, next_tril) -> smoothed belief at t (mean, scale_tril, status).
+
+    C = sum_s wc_s (X_s - m)(Y_s - m-)^T, G = C P-^-1, m^s = m + G (m^s_+ - m-),
+    P^s = P + G P^s_+ G^T - G P- G^T: n rank-1 updates of S by the columns of G S^s_+, then n
+    rank-1 downdates by the columns of G S- (updates first: every intermediate then dominates
+    P^s, where downdates first would pass through the nearly singular P - C P-^-1 C^T)."""
+    what = "ukf.rts_smooth"
+    _f32(what, mean, scale_tril, x_points, y_points, pred_mean, pred_tril, next_mean, next_tril)
+    if mean.ndim != 2:
+        raise RuntimeError(f"{what}: mean must be 2-D")
+    N, n = mean.shape
+    _shape(what, "scale_tril", scale_tril, (N, n, n))
+    _shape(what, "x_points", x_points, ((2 * n + 1) * N, n))
+    _shape(what, "y_points", y_points, ((2 * n + 1) * N, n))
+    _shape(what, "pred_mean", pred_mean, (N, n))
+    _shape(what, "pred_tril", pred_tril, (N, n, n))
+    _shape(what, "next_mean", next_mean, (N, n))
+    _shape(what, "next_tril", next_tril, (N, n, n))
+    _geo(what, N, n, groups)
+    mean, scale_tril, x_points, y_points, pred_mean, pred_tril, next_mean, next_tril = (
+        t.contiguous() for t in (mean, scale_tril, x_points, y_points, pred_mean, pred_tril,
+                                 next_mean, next_tril))
+    m1 = torch.empty_like(mean)
+    s1 = torch.empty_like(scale_tril)
+    status = torch.empty(N, device=mean.device, dtype=torch.int32)
+    check(lib.bpk_ukf_smooth_f32(mean.data_ptr(), scale_tril.data_ptr(), x_points.data_ptr(),
+                                 y_points.data_ptr(), pred_mean.data_ptr(), pred_tril.data_ptr(),
+                                 next_mean.data_ptr(), next_tril.data_ptr(), m1.data_ptr(),
+                                 s1.data_ptr(), status.data_ptr(), N, n, float(wc0), float(wi),
+                                 int(groups), stream_ptr(mean.device)), what)
     return m1, s1, status

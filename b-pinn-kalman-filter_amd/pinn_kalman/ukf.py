@@ -19,8 +19,15 @@ torchfilter here and are fixed as follows:
 
 One filter step is predict (sigma points -> dynamics -> unscented root) followed by update
 (sigma points redrawn from the prior -> measurement -> unscented root -> Kalman update); only
-libbpk.so kernels, the models and element-wise glue run on it.  `PINN_KF` (needs B_PINN ->
-bayesian_torch) and `InpaintKFMeasure` are not built.
+libbpk.so kernels, the models and element-wise glue run on it.
+
+Offline use (the reference filters a recorded sequence, pinn_kalman/ukf.py:85-138):
+`SquareRootUKF.filter` runs the forward steps over a whole sequence and keeps each step's
+posterior and prediction; `SquareRootUKF.smooth` then runs the unscented Rauch-Tung-Striebel
+recursion backwards over that history (`op.ukf.rts_smooth`), so the estimate at frame t also
+uses the frames after t.  `UKF.filter` / `UKF.smooth` are the same on fields, and
+`UKF(mask=...)` observes the density channel through `InpaintKFMeasure` (sparse pixels).
+`PINN_KF` (needs B_PINN -> bayesian_torch) is not built.
 """
 from __future__ import annotations
 
@@ -29,7 +36,22 @@ import torch.nn as nn
 
 from op import ukf as K
 
-from .ukf_utils import IdentityKFMeasure, NSDynamics, patch, unpatch
+from .ukf_utils import IdentityKFMeasure, InpaintKFMeasure, NSDynamics, patch, unpatch
+
+
+class FilterHistory:
+    """What `SquareRootUKF.filter` keeps of T steps, on the device: `means` [T+1, N, n] and
+    `scale_trils` [T+1, N, n, n] (index 0: the belief before the first step, index t + 1: the
+    posterior of step t), `pred_means` [T, N, n] and `pred_trils` [T, N, n, n] (the prediction
+    of step t) and `controls` (a list of length T)."""
+
+    def __init__(self, means, scale_trils, pred_means, pred_trils, controls):
+        self.means, self.scale_trils = means, scale_trils
+        self.pred_means, self.pred_trils = pred_means, pred_trils
+        self.controls = controls
+
+    def __len__(self):
+        return self.pred_means.shape[0]
 
 
 class SquareRootUKF(nn.Module):
@@ -47,6 +69,7 @@ class SquareRootUKF(nn.Module):
         self.alpha, self.beta, self.kappa = float(alpha), float(beta), float(kappa)
         self.groups = int(groups)
         self.belief_mean = self.belief_scale_tril = self.status = None
+        self._filtered = False
 
     def initialize_beliefs(self, mean, covariance=None, scale_tril=None):
         if (covariance is None) == (scale_tril is None):
@@ -110,6 +133,71 @@ class SquareRootUKF(nn.Module):
         self.update(observations)
         return self.belief_mean
 
+    @torch.no_grad()
+    def filter(self, observations, controls=None):
+        """T `forward` steps from the current belief over `observations` ([T, N, dz] or a
+        sequence of T tensors [N, dz]) and `controls` (None or a sequence of length T);
+        bit-identical to T calls of `forward`.  Returns the `FilterHistory` `smooth` needs."""
+        if self.belief_mean is None:
+            raise RuntimeError("SquareRootUKF: call initialize_beliefs first")
+        T = len(observations)
+        controls = [None] * T if controls is None else list(controls)
+        if len(controls) != T:
+            raise ValueError(f"SquareRootUKF.filter: {len(controls)} controls for {T} observations")
+        means, trils, pmeans, ptrils = [self.belief_mean], [self.belief_scale_tril], [], []
+        for t in range(T):
+            self.predict(controls[t])
+            pmeans.append(self.belief_mean)
+            ptrils.append(self.belief_scale_tril)
+            self.update(observations[t])
+            means.append(self.belief_mean)
+            trils.append(self.belief_scale_tril)
+        N, n = self.belief_mean.shape
+        dev = self.belief_mean.device
+        self._filtered = True
+        return FilterHistory(torch.stack(means), torch.stack(trils),
+                             torch.stack(pmeans) if T else torch.empty(0, N, n, device=dev),
+                             torch.stack(ptrils) if T else torch.empty(0, N, n, n, device=dev),
+                             controls)
+
+    @torch.no_grad()
+    def smooth(self, history):
+        """Unscented Rauch-Tung-Striebel smoother over a `filter` history -> (means_s
+        [T+1, N, n], scale_trils_s [T+1, N, n, n]); index T is the filtered posterior itself.
+
+        For t = T-1 .. 0 the sigma points of the posterior at t are redrawn and propagated
+        through the dynamics model again, then `op.ukf.rts_smooth` combines them with the
+        stored prediction and the smoothed belief at t + 1.  Redrawing instead of storing
+        keeps a step's history at 2 (N n^2 + N n) floats (76 MB at 2304 filters of n = 64,
+        against 228 MB with both point sets), and requires a deterministic dynamics model:
+        the second call must return the points the prediction was made from.  `NSDynamics`
+        is one.  Statuses are OR-ed into `self.status`."""
+        if self.belief_mean is None or not self._filtered:
+            raise RuntimeError("SquareRootUKF: call filter before smooth")
+        if not isinstance(history, FilterHistory):
+            raise ValueError("SquareRootUKF.smooth: history must come from filter()")
+        N, n = self.belief_mean.shape
+        T = len(history)
+        if (tuple(history.means.shape) != (T + 1, N, n)
+                or tuple(history.scale_trils.shape) != (T + 1, N, n, n)
+                or tuple(history.pred_means.shape) != (T, N, n)
+                or tuple(history.pred_trils.shape) != (T, N, n, n)
+                or len(history.controls) != T):
+            raise ValueError(f"SquareRootUKF.smooth: history is not one of {N} filters of "
+                             f"dimension {n}")
+        gamma, _, wc0, wi = self.weights
+        ms, Ss = [None] * (T + 1), [None] * (T + 1)
+        ms[T], Ss[T] = history.means[T], history.scale_trils[T]
+        for t in range(T - 1, -1, -1):
+            m, S = history.means[t], history.scale_trils[t]
+            x = K.sigma_points(m, S, gamma, self.groups)
+            y = self.dynamics_model(x, history.controls[t])[0]
+            ms[t], Ss[t], st = K.rts_smooth(m, S, x, y, history.pred_means[t],
+                                            history.pred_trils[t], ms[t + 1], Ss[t + 1], wc0, wi,
+                                            self.groups)
+            self.status |= st
+        return torch.stack(ms), torch.stack(Ss)
+
 
 class UKF(nn.Module):
     """The reference's patch filter (pinn_kalman/ukf.py:9-44): state = the p x p patches of the
@@ -119,15 +207,28 @@ class UKF(nn.Module):
 
     `initialize(x0, var)`: the reference passes `eye * var` as torchfilter's `covariance`;
     whether it meant a covariance or a factor cannot be settled without torchfilter, so it is
-    taken at its word: the initial scale_tril is sqrt(var) I."""
+    taken at its word: the initial scale_tril is sqrt(var) I.
 
-    def __init__(self, config, compat=True):
+    `mask` ([H, W] or [1, 1, H, W], 1 = observed; None = every pixel, the reference's filter):
+    the density channel is observed through `InpaintKFMeasure` and the density channel of
+    every observation is multiplied by the mask, so an unobserved pixel has zero measurement
+    deviation and zero innovation and is left to the dynamics.
+
+    `filter(obsv_seq)` / `smooth(obsv_seq)` process a recorded sequence [T, B, 4, H, W];
+    `smooth` needs a deterministic dynamics model (see `SquareRootUKF.smooth`)."""
+
+    def __init__(self, config, compat=True, mask=None):
         super().__init__()
         self.dim = config.kf.patch_size
         self.size = config.data.image_size
         self.device = config.device
         self.dynamic = NSDynamics(config, compat=compat)
-        self.measurement = IdentityKFMeasure(config)
+        self.mask = None
+        if mask is None:
+            self.measurement = IdentityKFMeasure(config)
+        else:
+            self.measurement = InpaintKFMeasure(config, mask)
+            self.mask = self.measurement.mask_field.to(self.device)
         self.ukf = SquareRootUKF(self.dynamic, self.measurement, alpha=1.0, beta=0.0, kappa=0.0,
                                  groups=4)
 
@@ -145,5 +246,27 @@ class UKF(nn.Module):
 
     def forward(self, obsv):
         """obsv [B, 4, H, W] -> filtered fields [B, 4, H, W]."""
-        pred = self.ukf(patch(obsv, self.dim))
+        pred = self.ukf(self._observation(obsv))
         return unpatch(pred, self.dim, self.size, 4)
+
+    def _observation(self, obsv):
+        """[B, 4, H, W] -> the filters' observation rows (density masked under `mask`)."""
+        if self.mask is not None:
+            obsv = torch.cat([obsv[:, :1] * self.mask, obsv[:, 1:]], dim=1)
+        return patch(obsv, self.dim)
+
+    def _fields(self, means):
+        """[T, N, n] -> [T, B, 4, H, W]."""
+        return torch.stack([unpatch(m, self.dim, self.size, 4) for m in means])
+
+    def filter(self, obsv_seq):
+        """obsv_seq [T, B, 4, H, W] -> filtered fields [T, B, 4, H, W]: T `forward` steps."""
+        self.history = self.ukf.filter([self._observation(o) for o in obsv_seq])
+        return self._fields(self.history.means[1:])
+
+    def smooth(self, obsv_seq):
+        """obsv_seq [T, B, 4, H, W] -> (filtered, smoothed), both [T, B, 4, H, W]: `filter`,
+        then the backward pass; smoothed[T-1] is filtered[T-1]."""
+        filtered = self.filter(obsv_seq)
+        means_s, _ = self.ukf.smooth(self.history)
+        return filtered, self._fields(means_s[1:])

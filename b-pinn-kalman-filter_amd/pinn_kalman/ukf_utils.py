@@ -5,8 +5,9 @@ What the square-root UKF (`pinn_kalman.ukf`, kernels in csrc/ukf.hip) calls on i
 advances the unpatched fields by one simulator step -- update_velocity, update_pressure,
 update_density (ukf_utils.py:109-111) -- here the fused `ns_step.full_step` (bit-identical to
 the three calls), and returns the re-patched state with the reference's constant process
-noise 1e-8 I, and `IdentityKFMeasure`, the identity observation model with per-channel noise.
-Both are plain nn.Modules with the torchfilter model call contract (`state_dim`,
+noise 1e-8 I, and `IdentityKFMeasure`, the identity observation model with per-channel noise
+(`InpaintKFMeasure`: the same with the density channel seen through a pixel mask).
+All are plain nn.Modules with the torchfilter model call contract (`state_dim`,
 `forward(states, ...) -> (states, noise)`); the second value is consumed by the filter as a
 lower-triangular square-root factor [rows, dim, dim].  The debug prints of the reference
 (NaN/inf checks, each a device sync) are dropped.
@@ -145,3 +146,32 @@ class IdentityKFMeasure(nn.Module):
         if factor_rows is not None:
             diag = diag[factor_rows]
         return states, torch.diag_embed(diag)
+
+
+class InpaintKFMeasure(IdentityKFMeasure):
+    """Sparse observation of the density channel (the intent of reference ukf_utils.py:69-82,
+    whose own version fails its operator's shape assert): `mask` [H, W] or [1, 1, H, W], 1 =
+    observed pixel.  The density rows of `states` -- the first quarter of the rows, or all of
+    them under `f_only` -- are multiplied by the patched mask tiled over the batch; the u, v and
+    p rows and the returned factor are the parent's.  An unobserved pixel then has the same
+    measurement (0) at every sigma point: zero measurement deviation, and with the observation
+    masked the same way zero innovation, so the update leaves it to the dynamics."""
+
+    def __init__(self, config, mask, noisy=False):
+        super().__init__(config, noisy=noisy)
+        mask = torch.as_tensor(mask, dtype=torch.float32)
+        if mask.ndim == 2:
+            mask = mask[None, None]
+        if tuple(mask.shape) != (1, 1, self.size, self.size):
+            raise ValueError(f"InpaintKFMeasure: mask must be [{self.size}, {self.size}] or "
+                             f"[1, 1, {self.size}, {self.size}], got {list(mask.shape)}")
+        self.mask_field = mask
+        self.mask = patch(mask, self.dim).contiguous()  # [patches, dim]
+
+    def forward(self, states, f_only=False, factor_rows=None):
+        z, factor = super().forward(states, f_only=f_only, factor_rows=factor_rows)
+        q = z.shape[0] if f_only else z.shape[0] // 4
+        m = self._tiled(self.mask, q, z.device)
+        if f_only:
+            return z * m, factor
+        return torch.cat([z[:q] * m, z[q:]], dim=0), factor

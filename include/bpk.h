@@ -787,6 +787,16 @@ int bpk_instance_norm_act_bwd2_f64(const double* v, const double* dy, const doub
  *   update: P_xz = sum_s wc_s (X_s - m)(Z_s - zhat)^T, U = P_xz S_z^-T (= K S_z),
  *           m+ = m + U S_z^-1 (z - zhat) (= m + K (z - zhat)), S+ = S after one rank-1
  *           downdate per column of U.
+ *   smooth: one backward step t+1 -> t of the unscented Rauch-Tung-Striebel smoother.
+ *           (m, S) the posterior at t, X its sigma points, Y = f(X), (m-, S-) the stored
+ *           prediction at t+1 (root of Y), (m^s_+, S^s_+) the smoothed belief at t+1:
+ *           C = sum_s wc_s (X_s - m)(Y_s - m-)^T, U = C S-^-T (the gain G = U S-^-1 is never
+ *           formed), m^s = m + U S-^-1 (m^s_+ - m-) (= m + G (m^s_+ - m-)),
+ *           W = U S-^-1 S^s_+ (= G S^s_+), S^s = S after one rank-1 update per column of W
+ *           (in order) and then one rank-1 downdate per column of U (in order):
+ *           P^s = P + G P^s_+ G^T - G P- G^T.  Updates come first so that every
+ *           intermediate dominates P^s; downdates first would pass through the Schur
+ *           complement P - C P-^-1 C^T, nearly singular when the process noise is small.
  * status [N] int32 is written 0, or 1 where a downdate met S_kk^2 - x_k^2 <= 0: that
  * diagonal becomes eps_f32 |S_kk|, the rest of that vector is dropped, the filter's
  * outputs are finite but otherwise unspecified, and other filters are unaffected.
@@ -801,6 +811,11 @@ int bpk_ukf_update_f32(const float* mean, const float* scale_tril, const float* 
                        const float* z_points, const float* z_mean, const float* z_tril,
                        const float* obs, float* mean_out, float* scale_tril_out, int* status,
                        int64_t N, int n, int dz, float wc0, float wi, int groups, void* stream);
+int bpk_ukf_smooth_f32(const float* mean, const float* scale_tril, const float* x_points,
+                       const float* y_points, const float* pred_mean, const float* pred_tril,
+                       const float* next_mean, const float* next_tril, float* mean_out,
+                       float* scale_tril_out, int* status, int64_t N, int n, float wc0, float wi,
+                       int groups, void* stream);
 
 #ifdef __cplusplus
 }
