@@ -29,6 +29,7 @@
 // follows the update with draw id d.  The data draw uses the same global element
 // index as the update draw; colorization consumes only channel 0's elements.
 #include "bpk_common.h"
+#include "philox.h"
 
 #include <algorithm>
 
@@ -36,40 +37,7 @@
 
 namespace {
 
-__device__ inline uint4 philox4x32_10(uint4 ctr, uint2 key) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  constexpr uint32_t W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, ctr.x), lo0 = M0 * ctr.x;
-    const uint32_t hi1 = __umulhi(M1, ctr.z), lo1 = M1 * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += W0;
-    key.y += W1;
-  }
-  return ctr;
-}
-
-__device__ inline float u01(uint32_t r) {  // (0, 1]
-  return ((float)(r >> 8) + 1.0f) * (1.0f / 16777216.0f);
-}
-
-// normal of global element index ge (4 per Philox block)
-__device__ inline void normal4(uint64_t q, int step, int draw, uint64_t seed, float out[4]) {
-  const uint4 r = philox4x32_10(make_uint4((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)step,
-                                           (uint32_t)draw),
-                                make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-  const float two_pi = 6.283185307179586f;
-  const float r0 = sqrtf(-2.0f * logf(u01(r.x)));
-  const float r1 = sqrtf(-2.0f * logf(u01(r.z)));
-  float s0, c0, s1, c1;
-  sincosf(two_pi * u01(r.y), &s0, &c0);
-  sincosf(two_pi * u01(r.w), &s1, &c1);
-  out[0] = r0 * c0;
-  out[1] = r0 * s0;
-  out[2] = r1 * c1;
-  out[3] = r1 * s1;
-}
+using bpk::normal4;
 
 __device__ inline float noise_at(const float* noise, int64_t i, int64_t ge, int step, int draw,
                                  uint64_t seed) {

@@ -268,16 +268,24 @@ def _observe(config, operator, f, noise=None):
 def get_prelim_step_fn(config, train, optimize_fn, is_bpinn=False, ctx=None):
     """Schedule 1 of PINN training: data losses of FlowNet and PressureNet, each with its
     own Adam (reference losses.py:233-329).  Returns step_fn(state, operator, batch) ->
-    (loss, v_loss, p_loss) with batch = (f1, f2, x, y, t, target)."""
-    if is_bpinn:
-        raise NotImplementedError("B-PINN needs bayesian_torch (not on the MI355X hot path)")
+    (loss, v_loss, p_loss) with batch = (f1, f2, x, y, t, target).  is_bpinn (a B_PINN model):
+    v_loss gains 0.1 KL_flow / batch_size and p_loss 0.01 KL_pres / batch_size, the KL of each
+    forward's weight draw."""
     error_fn = torch.nn.MSELoss()
+
+    def kl_loss_fn(model):
+        # KL of the forward's weight draw (models/bayesian.py), per sample of the configured
+        # batch (reference losses.py:237-242)
+        return model.kl_loss() / config.training.batch_size
 
     def flow_loss_fn(model, operator, batch):
         f1, f2, x, y, t, target = batch
         f1 = _observe(config, operator, f1)
         f2 = _observe(config, operator, f2)
-        return model.multiscale_data_mse(model(f1, f2, x, y, t), target, error_fn=error_fn)
+        v_loss = model.multiscale_data_mse(model(f1, f2, x, y, t), target, error_fn=error_fn)
+        if is_bpinn:
+            return v_loss + kl_loss_fn(model) * 0.1
+        return v_loss
 
     def pres_loss_fn(model, batch):
         f1, f2, x, y, t, target = batch
@@ -287,7 +295,10 @@ def get_prelim_step_fn(config, train, optimize_fn, is_bpinn=False, ctx=None):
             pyramid.append(torch.nn.functional.interpolate(
                 flow, size=(flow.shape[2] // 2, flow.shape[3] // 2), mode="bilinear",
                 align_corners=False))
-        return model.data_mse(model(pyramid[::-1], x, y, t), target, error_fn=error_fn)
+        p_loss = model.data_mse(model(pyramid[::-1], x, y, t), target, error_fn=error_fn)
+        if is_bpinn:
+            return p_loss + kl_loss_fn(model) * 0.01
+        return p_loss
 
     def step_fn(state, operator, batch):
         model = state["model"]

@@ -8,14 +8,17 @@ first order with create_graph (so they train the nets), second order without
 (SURVEY.md Appendix A.5-6).  The second derivative through the warping runs on
 the HIP grid_sample grad2 kernel.
 
-Only the deterministic PINN is built: B_PINN needs `bayesian_torch` (unpinned,
-absent here) and is out of scope.
+`B_PINN(config, pretrained_pinn=None)` (reference pinn.py:116-185): the same nets with every
+conv replaced by a Bayesian stand-in (models/bayesian.py; one fused HIP launch draws all
+weights of a net and reduces its KL, op.bayes), `sample_uvp` / `predict` for the Monte-Carlo
+mean and standard deviation that `PINN_KF` feeds to the filter.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
+from models.bayesian import dnn_to_bnn
 from models.flownet import FlowNet, PressureNet, project
 
 # diagnostics hook (tools/prof_pinn_phases.py): called with a phase name between the residual's
@@ -218,3 +221,63 @@ class PINN(nn.Module):
     def step(self, ft, u):
         """Advance a field by the predicted flow (reference pinn.py:113-114)."""
         return project(ft, u, self.dt)
+
+
+class B_PINN(PINN):
+    """Bayesian PINN (reference pinn.py:116-185).  Priors as there: FlowNet N(0, 0.1) with
+    rho initialised at -3, PressureNet N(0, 0.01) with rho at -0.5; with `pretrained_pinn`
+    its nets are taken over and initialised by MOPED (mu = the trained weights,
+    sigma = config.model.bpinn_moped_delta |w|).
+
+    Every forward of a net draws ONE sample of all its weights (models/bayesian.py), in
+    train() and eval() alike; `flownet.kl_loss()` / `pressurenet.kl_loss()` return the KL of
+    the last draw.  `reseed(seed, step=0)` resets both noise streams (FlowNet on Philox key
+    2 seed, PressureNet on 2 seed + 1), which depend on nothing else -- not on the rank.
+
+    Only the data-loss schedule trains it (losses.get_prelim_step_fn(is_bpinn=True)); the
+    residual schedule (get_pinn_step_fn / equation_mse) is out of scope.
+    """
+
+    def __init__(self, config, pretrained_pinn: PINN = None, seed=0):
+        self.using_pretrained = pretrained_pinn is not None
+        super().__init__(config)
+        prior = {"prior_mu": 0.0, "type": "Reparameterization", "posterior_mu_init": 0.0,
+                 "moped_enable": self.using_pretrained,
+                 "moped_delta": config.model.bpinn_moped_delta}
+        flow_prior = dict(prior, prior_sigma=0.1, posterior_rho_init=-3.0)
+        pres_prior = dict(prior, prior_sigma=0.01, posterior_rho_init=-0.5)
+        if self.using_pretrained:
+            self.flownet = pretrained_pinn.flownet
+            self.pressurenet = pretrained_pinn.pressurenet
+        dnn_to_bnn(self.flownet, flow_prior)
+        dnn_to_bnn(self.pressurenet, pres_prior)
+        self.flownet = self.flownet.to(config.device)
+        self.pressurenet = self.pressurenet.to(config.device)
+        self.batch = config.training.batch_size
+        self.reseed(seed)
+
+    def reseed(self, seed, step=0):
+        self.flownet.bayes.reseed(2 * int(seed), step)
+        self.pressurenet.bayes.reseed(2 * int(seed) + 1, step)
+
+    def sample_uvp(self, f1, f2, x, y, t, n=64, size=None):
+        """n Monte-Carlo runs -> (list of n full-size flows, list of n pressures)."""
+        flow_pred, pres_pred = [], []
+        for _ in range(n):
+            flow, pressure = self.forward(f1, f2, x, y, t, size)
+            flow_pred.append(flow[-1])
+            pres_pred.append(pressure)
+        return flow_pred, pres_pred
+
+    def predict(self, f1, f2, x, y, t, n=64):
+        """(flow mean, pressure mean, next-frame mean, flow std, pressure std, next-frame std)
+        over n Monte-Carlo runs; std is torch.std's (unbiased)."""
+        flow_pred, pres_pred = self.sample_uvp(f1, f2, x, y, t, n)
+        f_pred = torch.stack([self.step(f2, flow) for flow in flow_pred], dim=0)
+        flow_pred = torch.stack(flow_pred, dim=0)
+        pres_pred = torch.stack(pres_pred, dim=0)
+        return (flow_pred.mean(dim=0), pres_pred.mean(dim=0), f_pred.mean(dim=0),
+                flow_pred.std(dim=0), pres_pred.std(dim=0), f_pred.std(dim=0))
+
+    def uncertainty(self, flow, pres):
+        return 0

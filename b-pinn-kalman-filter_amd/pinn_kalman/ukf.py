@@ -27,7 +27,10 @@ posterior and prediction; `SquareRootUKF.smooth` then runs the unscented Rauch-T
 recursion backwards over that history (`op.ukf.rts_smooth`), so the estimate at frame t also
 uses the frames after t.  `UKF.filter` / `UKF.smooth` are the same on fields, and
 `UKF(mask=...)` observes the density channel through `InpaintKFMeasure` (sparse pixels).
-`PINN_KF` (needs B_PINN -> bayesian_torch) is not built.
+
+`PINN_KF` (reference :46-82) couples the filter to a `B_PINN`: each step the Monte-Carlo mean
+of the predicted flow and pressure is the pseudo-observation of (u, v, p) and their standard
+deviation the observation's uncertainty (`IdentityKFMeasure.update_uncertainty`).
 """
 from __future__ import annotations
 
@@ -36,6 +39,7 @@ import torch.nn as nn
 
 from op import ukf as K
 
+from .pinn import B_PINN
 from .ukf_utils import IdentityKFMeasure, InpaintKFMeasure, NSDynamics, patch, unpatch
 
 
@@ -270,3 +274,45 @@ class UKF(nn.Module):
         filtered = self.filter(obsv_seq)
         means_s, _ = self.ukf.smooth(self.history)
         return filtered, self._fields(means_s[1:])
+
+
+class PINN_KF(nn.Module):
+    """B-PINN pseudo-observations filtered by the patch UKF (reference pinn_kalman/ukf.py:46-82).
+
+    `initialize(f, v, p, var=1e-2)`: the filter starts at the patched fields [f, v, p] with
+    scale sqrt(var) I, and f becomes the previous frame.  It loads no checkpoint: the reference
+    hard-codes a path (and uses names it never defines); loading the B_PINN's weights
+    (`self.pinn`, e.g. utils.load_checkpoint) is the caller's job.
+
+    `forward(x, y, t, f, n=8)`, without autograd: n Monte-Carlo forwards of the B_PINN on
+    (previous frame, f); mean and unbiased std of the full-size flow and of the pressure; the
+    stds go to `measurement.update_uncertainty`; the observation cat[f, flow mean, pressure
+    mean] goes through one `UKF.forward`.  Returns the filtered fields [B, 4, H, W].
+    `mask` / `compat` are the UKF's."""
+
+    def __init__(self, config, compat=True, mask=None):
+        super().__init__()
+        self.device = config.device
+        self.patch_size = config.kf.patch_size
+        self.ukf = UKF(config, compat=compat, mask=mask).to(self.device)
+        self.pinn = B_PINN(config).to(self.device)
+        self.f_prev = None
+
+    def initialize(self, f, v, p, var=1e-2):
+        state = patch(torch.cat([f, v, p], dim=1), self.patch_size)
+        self.ukf.initialize(state, var)
+        self.f_prev = f
+
+    @torch.no_grad()
+    def forward(self, x, y, t, f, n=8):
+        if self.f_prev is None:
+            self.f_prev = torch.ones_like(f) * 0.1
+        t = t.to(self.device)
+        flow, pres = self.pinn.sample_uvp(self.f_prev, f, x, y, t, n=n,
+                                          size=(self.ukf.size, self.ukf.size))
+        flow, pres = torch.stack(flow, dim=0), torch.stack(pres, dim=0)
+        flow_uncer, pres_uncer = flow.std(dim=0), pres.std(dim=0)
+        flow, pres = flow.mean(dim=0), pres.mean(dim=0)
+        self.f_prev = f
+        self.ukf.measurement.update_uncertainty(flow_uncer, pres_uncer)
+        return self.ukf(torch.cat([f, flow, pres], dim=1))

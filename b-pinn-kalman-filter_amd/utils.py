@@ -77,6 +77,36 @@ def load_checkpoint(ckpt_dir, model, device):
     return model
 
 
+def restore_bpinn_checkpoint(pinn_ckpt_dir, bpinn_ckpt_dir, state, config):
+    """Resume a B-PINN run (reference utils.py:62-92): from `bpinn_ckpt_dir` if it exists (the
+    state's B_PINN, both optimizers, EMA and step are loaded in place); else from a trained
+    deterministic PINN at `pinn_ckpt_dir` -- a fresh B_PINN initialised by MOPED from it and two
+    new optimizers replace state['model'] / state['optimizer']; else the state is returned
+    unchanged."""
+    if os.path.exists(bpinn_ckpt_dir):
+        loaded = _load(bpinn_ckpt_dir, config.device)
+        state["optimizer"][0].load_state_dict(loaded["optimizer_1"])
+        state["optimizer"][1].load_state_dict(loaded["optimizer_2"])
+        state["model"].load_state_dict(loaded["model"], strict=False)
+        state["ema"].load_state_dict(loaded["ema"])
+        state["step"] = loaded["step"]
+        return state
+    if not os.path.exists(pinn_ckpt_dir):
+        logging.warning(f"No B-PINN checkpoint at {bpinn_ckpt_dir} and no PINN checkpoint at "
+                        f"{pinn_ckpt_dir}: state left as it is")
+        return state
+    import losses
+    from pinn_kalman import pinn
+    pretrained = load_checkpoint(pinn_ckpt_dir, pinn.PINN(config), config.device)
+    model = pinn.B_PINN(config, pretrained)
+    state["model"] = model
+    state["optimizer"] = (
+        losses.get_optimizer(config, model.flownet.parameters(), is_bpinn=True),
+        losses.get_optimizer(config, model.pressurenet.parameters(), is_bpinn=True, lr_mul=.05))
+    logging.warning(f"B-PINN initialised by MOPED from the PINN checkpoint {pinn_ckpt_dir}")
+    return state
+
+
 def save_checkpoint(ckpt_dir, state):
     if isinstance(state["optimizer"], tuple):
         saved = {"info": 0, "optimizer_1": state["optimizer"][0].state_dict(),

@@ -817,6 +817,36 @@ int bpk_ukf_smooth_f32(const float* mean, const float* scale_tril, const float* 
                        float* scale_tril_out, int* status, int64_t N, int n, float wc0, float wi,
                        int groups, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * bayes: mean-field Gaussian (reparameterized) weights of one network.  mu, rho, W, gW,
+ * gmu, grho are flat float32 vectors of P elements; `table` is float64 [S, 4] on the
+ * device, one row per segment (a layer's kernel or bias): (offset, numel, prior_mu,
+ * prior_sigma), offsets ascending from 0 and the segments tiling [0, P) (any offsets: not
+ * multiples of 4).  Stands in for bayesian_torch's Conv2dReparameterization /
+ * ConvTranspose2dReparameterization + get_kl_loss behind the reference's B_PINN
+ * (pinn_kalman/pinn.py:116-148).
+ *   sample_kl    : sigma = softplus(rho) (finite and positive for rho in [-100, 30]),
+ *                  W[e] = mu[e] + sigma[e] eps[e],
+ *                  kl[0] = sum over segments of the mean over the segment of
+ *                          log(sp / sigma) + (sigma^2 + (mu - mp)^2) / (2 sp^2) - 1/2.
+ *                  `ws`: bpk_bayes_workspace_bytes(P) bytes of scratch (block partials).
+ *   sample_kl_bwd: gmu  = gW + gkl[0] (mu - mp) / (sp^2 n_seg),
+ *                  grho = (gW eps + gkl[0] (sigma / sp^2 - 1 / sigma) / n_seg) sigmoid(rho).
+ *                  gW or gkl may be NULL (taken as zero).
+ * eps[e] is what bpk_philox_normal_f32(out, 1, P, 0, seed, &step, 0) writes at out[e]; it is
+ * not stored, the backward draws it again from (seed, step).  The KL is reduced in a fixed
+ * order (block partials, then a one-block second launch): no atomics, bitwise reproducible.
+ * float4 accesses when the vectors are 16-byte aligned, scalar ones otherwise.
+ * Asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+int64_t bpk_bayes_workspace_bytes(int64_t P);
+int bpk_bayes_sample_kl_f32(const float* mu, const float* rho, const double* table, int S,
+                            int64_t P, uint64_t seed, int step, float* W, float* kl, void* ws,
+                            void* stream);
+int bpk_bayes_sample_kl_bwd_f32(const float* mu, const float* rho, const double* table, int S,
+                                int64_t P, uint64_t seed, int step, const float* gW,
+                                const float* gkl, float* gmu, float* grho, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
