@@ -505,20 +505,23 @@ __global__ __launch_bounds__(256, NB == 1 ? 2 : 1) void wino_f23_kernel(const fl
 constexpr unsigned kTsMax = 1u << 17;
 __device__ long long g_wino_ts[kTsMax][8];
 __device__ unsigned g_wino_cu[kTsMax];
-#define WINO_TS(slot)                                                              \
+// WINO_TS_AT(rec, slot): the record index is the item where a workgroup walks several
+// (k16_item24); WINO_TS(slot) keeps one record per workgroup.
+#define WINO_TS_AT(rec, slot)                                                      \
   do {                                                                             \
-    if (threadIdx.x == 0 && blockIdx.x < kTsMax) {                                 \
-      g_wino_ts[blockIdx.x][slot] = wall_clock64();                                \
-      if (slot == 0) g_wino_cu[blockIdx.x] = __smid();                             \
+    if (threadIdx.x == 0 && (rec) < kTsMax) {                                      \
+      g_wino_ts[rec][slot] = wall_clock64();                                       \
+      if (slot == 0) g_wino_cu[rec] = __smid();                                    \
       if (slot == 0 || slot == 5)                                                  \
-        g_wino_ts[blockIdx.x][6 + slot / 5] = (long long)__builtin_amdgcn_s_memtime(); \
+        g_wino_ts[rec][6 + slot / 5] = (long long)__builtin_amdgcn_s_memtime();    \
     }                                                                              \
   } while (0)
 #else
-#define WINO_TS(slot) \
-  do {                \
+#define WINO_TS_AT(rec, slot) \
+  do {                        \
   } while (0)
 #endif
+#define WINO_TS(slot) WINO_TS_AT(blockIdx.x, slot)
 
 // Software-pipelined form (one workgroup per CU, 4 waves x 32 couts = 128 couts, 32 tiles).
 // The serial form above runs store-patch | barrier | transform | barrier | MFMAs per chunk,
@@ -1217,12 +1220,52 @@ __global__ __launch_bounds__(512, 1) void wino_f23_k16_kernel(
 constexpr int kM24 = 16;   // tiles per region
 constexpr int kVS24 = 28;  // LDS stride of one (cin, tile) V record (24 + pad)
 
-template <bool PRE>
+// The item boundary (prologue, last steps, epilogue) of k16_item24, one switch per part; a
+// part set to 0 compiles the earlier form (A/B builds, tools/build_variant.sh).  No part
+// changes an operand or the order of an accumulation.
+//   WINO_F24_PRO_ORDER  the prologue issues the GroupNorm table load first, then patch(0), then
+//                       the rest, so the first patch store waits for those two only (loads
+//                       return in issue order); patch(1) is activated after V(0) is written
+//   WINO_F24_TAIL       steps nch-3 .. nch-1 are peeled (TAIL 1..3) without the loads, patch
+//                       stores, transform and filter refills of chunks that do not exist; in the
+//                       TAILK instantiation, which the host picks for even chunk counts (every
+//                       conv of the nets): odd counts keep the full-step schedule
+//   WINO_F24_UNEXT      needs TAIL: the filter refills of the last step's k-steps 2 and 3 fetch
+//                       k-steps 0 and 1 of this slice's first chunk again; the prologue of the
+//                       workgroup's next item loads no filter when that item has the same
+//                       cout block and split-K slice (a scalar test, once per item)
+//   WINO_F24_KEEP_TAB   the GroupNorm table in LDS is reloaded only when the image changes
+#ifndef WINO_F24_PRO_ORDER
+#define WINO_F24_PRO_ORDER 1
+#endif
+#ifndef WINO_F24_TAIL
+#define WINO_F24_TAIL 1
+#endif
+#ifndef WINO_F24_UNEXT
+#define WINO_F24_UNEXT 1
+#endif
+#ifndef WINO_F24_KEEP_TAB
+#define WINO_F24_KEEP_TAB 1
+#endif
+
+// What one workgroup carries from item to item of its walk: the image whose table is in LDS
+// and, when `u_ready`, the first two filter k-steps of the coming item in `uo`.
+struct Item24Carry {
+  f4 uo[2][6];
+  int tab_n;
+  bool u_ready;
+};
+
+template <bool PRE, bool TAILK>
 __device__ __forceinline__ void k16_item24(
-    unsigned b, const float* __restrict__ x, const float* __restrict__ U,
+    unsigned b, unsigned nb, const float* __restrict__ x, const float* __restrict__ U,
     const float* __restrict__ bias, const float* __restrict__ skip,
     const float2* __restrict__ pre, float* __restrict__ y, float2* __restrict__ stats,
-    const WinoGeo& g, const float* __restrict__ x2) {
+    const WinoGeo& g, const float* __restrict__ x2, Item24Carry& carry) {
+  constexpr bool kOrder = WINO_F24_PRO_ORDER != 0, kTail = WINO_F24_TAIL != 0 && TAILK;
+  constexpr bool kUNext = kTail && WINO_F24_UNEXT != 0, kKeepTab = WINO_F24_KEEP_TAB != 0;
+  constexpr int kOob = (int)0x80000000u;  // buffer offset past every tensor: the load returns 0
+                                          // and fetches nothing
   constexpr int CK = 16;
   constexpr int kPatch = CK * kPR * kPCp;
   __shared__ __attribute__((aligned(16))) float s_patch_raw[2][kPatch];
@@ -1242,6 +1285,16 @@ __device__ __forceinline__ void k16_item24(
   const int oy0 = (int)ry * kOutRows, ox0 = (int)rx * kOutCols;
   const int cout_w = (int)cb * 128 + wave * 16;
   const int ph = __builtin_amdgcn_readfirstlane(tid >> 8);  // channels 8 ph .. 8 ph + 7
+  WINO_TS_AT(b, 0);
+  // does the workgroup's next item (nb, ~0u = none) read the same filter slice as this one?
+  bool u_next = false;
+  if (kUNext && nb != ~0u) {
+    unsigned cb2, t2;
+    unsigned r2 = udivmod(nb, (unsigned)g.cout_blocks, cb2);
+    r2 = udivmod(r2, (unsigned)g.regions_x, t2);
+    r2 = udivmod(r2, (unsigned)g.regions_y, t2);
+    u_next = cb2 == cb && (int)udivmod(r2, (unsigned)g.N, t2) == ks_idx;
+  }
 
   f4 acc[24];
   const int64_t plane = (int64_t)g.H * g.W;
@@ -1277,14 +1330,17 @@ __device__ __forceinline__ void k16_item24(
     pdst = py * kPCp + px + ph * 8 * (kPR * kPCp);
   }
   float pv[8];
-  auto load_patch_part = [&](float* dst, int k, int c0, int cn) {
+  // guard (the prologue of TAIL builds): a chunk past the last is requested out of range, which
+  // fetches nothing and keeps the number of loads in flight the same for every nch
+  auto load_patch_part = [&](float* dst, int k, int c0, int cn, bool guard = false) {
     const int cc = (kb + min(k, nch - 1)) * CK;
     const bool second = cc >= g.C1;
     const int soff = ((second ? cc - g.C1 : cc) + ph * 8) * (int)xplane * 4;
+    const int po = (guard && k >= nch) ? kOob : poff;
 #pragma unroll
     for (int c = c0; c < c0 + cn; ++c)
       dst[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-          second ? xrs2 : xrs, poff, soff + c * (int)xplane * 4, 0));
+          second ? xrs2 : xrs, po, soff + c * (int)xplane * 4, 0));
   };
   auto store_patch_part = [&](const float* src, float* sp, int k, int c0, int cn) {
     const int cb0 = (kb + min(k, nch - 1)) * CK + ph * 8;
@@ -1300,11 +1356,13 @@ __device__ __forceinline__ void k16_item24(
   };
   // B operands: uo[ks & 1][q] = points 4q..4q + 3 of U24 (cin c0 + 4 ks + kq, cout cout_w + jj),
   // at [cin][cout_w / 16][q][jj] (wino_filter24_kernel): 256 contiguous bytes per kq
-  f4 uo[2][6];
+  f4(&uo)[2][6] = carry.uo;
   const int uoff = ((kq * g.Cout + cout_w) * 24 + jj * 4) * 4;
   auto u_soff = [&](int k, int ks) {
     return (((kb + min(k, nch - 1)) * CK + 4 * ks) * g.Cout) * 96;
   };
+  const int u_soff0[2] = {__builtin_amdgcn_readfirstlane(u_soff(0, 0)),
+                          __builtin_amdgcn_readfirstlane(u_soff(0, 1))};
   auto load_u = [&](int slot, int k, int ks) {
     const int soff = u_soff(k, ks);
 #pragma unroll
@@ -1344,24 +1402,64 @@ __device__ __forceinline__ void k16_item24(
   };
 
   // prologue: V(0) in s_v[0], patch(1) in s_patch[1], patch(2) and U(0) in flight
-  {
+  const bool tab_load = PRE && !(kKeepTab && carry.tab_n == n);
+  const bool u_have = kUNext && carry.u_ready;  // uo[0], uo[1] came with the previous item
+  carry.tab_n = n;
+  carry.u_ready = u_next;
+  if (kOrder) {
+    // loads return in issue order: the table and patch(0), which the first stores need, go
+    // first and the filter (98 KB per workgroup) last
+    float pv0[8], pv1[8];
+    float2 tv[kPreMaxCin / 512];
+    if (tab_load) {
+#pragma unroll
+      for (int i = 0; i < kPreMaxCin / 512; ++i) tv[i] = pre_n[min(tid + 512 * i, g.Cin - 1)];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_patch_part(pv0, 0, 0, 8);
+    __builtin_amdgcn_sched_barrier(0);
+    load_patch_part(pv1, 1, 0, 8, kTail);
+    load_patch_part(pv, 2, 0, 8, kTail);
+    // the filter only where the previous item did not fetch it: in place, under a branch, so
+    // that no copy of uo (a wait for every load) is needed where the two cases join; the wait
+    // for patch(0) below is exact for the common case, the one without these loads
+    if (!u_have) {
+      load_u(0, 0, 0);
+      load_u(1, 0, 1);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (tab_load) {
+#pragma unroll
+      for (int i = 0; i < kPreMaxCin / 512; ++i)
+        if (tid + 512 * i < g.Cin) s_ss[tid + 512 * i] = tv[i];
+      __syncthreads();
+    }
+    store_patch_part(pv0, s_patch_raw[0], 0, 0, 8);
+    __syncthreads();
+    read_d(s_patch_raw[0]);
+    write_v(s_v[0]);
+    if (!kTail || nch > 1) store_patch_part(pv1, s_patch_raw[1], 1, 0, 8);  // for step 0
+  } else {
     float pv0[8], pv1[8];
     load_patch_part(pv0, 0, 0, 8);
-    load_patch_part(pv1, 1, 0, 8);
-    load_patch_part(pv, 2, 0, 8);
-    load_u(0, 0, 0);
-    load_u(1, 0, 1);
-    if (PRE) {
+    load_patch_part(pv1, 1, 0, 8, kTail);
+    load_patch_part(pv, 2, 0, 8, kTail);
+    if (!u_have) {
+      load_u(0, 0, 0);
+      load_u(1, 0, 1);
+    }
+    if (tab_load) {
       for (int c = tid; c < g.Cin; c += 512) s_ss[c] = pre_n[c];
       __syncthreads();
     }
     store_patch_part(pv0, s_patch_raw[0], 0, 0, 8);
-    store_patch_part(pv1, s_patch_raw[1], 1, 0, 8);
+    if (!kTail || nch > 1) store_patch_part(pv1, s_patch_raw[1], 1, 0, 8);
+    __syncthreads();
+    read_d(s_patch_raw[0]);
+    write_v(s_v[0]);
   }
   __syncthreads();
-  read_d(s_patch_raw[0]);
-  write_v(s_v[0]);
-  __syncthreads();
+  WINO_TS_AT(b, 1);
 
   // A operands: points 4q..4q + 3 of the record (cin 4 ks + kq, tile jj), in a ring of four
   // registers quads over the chunk's 24 (ks, q) fragments: fragment i sits in a[i & 3] and is
@@ -1375,20 +1473,23 @@ __device__ __forceinline__ void k16_item24(
 #pragma unroll
     for (int q = 0; q < 4; ++q) a[q] = src[q];
   }
-  auto step = [&](int k, auto sb_c, auto first_c) __attribute__((always_inline)) {
+  // TL (TAIL builds): 0 = a full step; 1 / 2 / 3 = step nch - 3 / nch - 2 / nch - 1, which has
+  // no patch(k+3) to load / nor a patch(k+2) to store / nor any chunk k + 1
+  auto step = [&](int k, auto sb_c, auto first_c, auto tail_c) __attribute__((always_inline)) {
     constexpr int SB = decltype(sb_c)::value;
     constexpr bool FIRST = decltype(first_c)::value;
+    constexpr int TL = decltype(tail_c)::value;
     const float* sv = s_v[SB];
 #pragma unroll
     for (int grp = 0; grp < 8; ++grp) {  // 12 MFMAs each: k-step grp / 2, points 12 (grp & 1) ..
       const int ks = grp >> 1, hf = grp & 1;
       __builtin_amdgcn_sched_barrier(0);
-      if (grp == 0) read_d(s_patch_raw[SB ^ 1]);                        // patch(k+1)
-      if (grp == 1) write_v(s_v[SB ^ 1]);                               // V(k+1)
-      if (grp == 2) store_patch_part(pv, s_patch_raw[SB], k + 2, 0, 4);  // patch(k+2)
-      if (grp == 3) store_patch_part(pv, s_patch_raw[SB], k + 2, 4, 4);
-      if (grp == 4) load_patch_part(pv, k + 3, 0, 4);
-      if (grp == 5) load_patch_part(pv, k + 3, 4, 4);
+      if (grp == 0 && TL < 3) read_d(s_patch_raw[SB ^ 1]);                        // patch(k+1)
+      if (grp == 1 && TL < 3) write_v(s_v[SB ^ 1]);                               // V(k+1)
+      if (grp == 2 && TL < 2) store_patch_part(pv, s_patch_raw[SB], k + 2, 0, 4);  // patch(k+2)
+      if (grp == 3 && TL < 2) store_patch_part(pv, s_patch_raw[SB], k + 2, 4, 4);
+      if (grp == 4 && TL < 1) load_patch_part(pv, k + 3, 0, 4);
+      if (grp == 5 && TL < 1) load_patch_part(pv, k + 3, 4, 4);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int qq = 0; qq < 3; ++qq) {
@@ -1400,26 +1501,62 @@ __device__ __forceinline__ void k16_item24(
               a[fi & 3][pp], uo[ks & 1][q][pp],
               (FIRST && ks == 0) ? f4{0.f, 0.f, 0.f, 0.f} : acc[4 * q + pp], 0, 0, 0);
         if (fi + 4 < 24) a[fi & 3] = a_src(sv, (fi + 4) / 6)[(fi + 4) % 6];
-        // k-step ks + 2 of this chunk, or ks - 2 of the next
-        const int soff = ks < 2 ? u_soff(k, ks + 2) : u_soff(k + 1, ks - 2);
-        uo[ks & 1][q] = __builtin_bit_cast(
-            f4, __builtin_amdgcn_raw_buffer_load_b128(urs, uoff + q * 256, soff, 0));
+        // k-step ks + 2 of this chunk, or ks - 2 of the next; after the last chunk (UNEXT) of
+        // this slice's first chunk again, which is what the workgroup's next item starts with
+        // when u_next (otherwise 98 KB read for nothing, once or twice per workgroup and launch)
+        if (ks < 2 || TL < 3 || kUNext) {
+          const int soff = ks < 2 ? u_soff(k, ks + 2)
+                                  : (TL < 3 ? u_soff(k + 1, ks - 2) : u_soff0[ks - 2]);
+          uo[ks & 1][q] = __builtin_bit_cast(
+              f4, __builtin_amdgcn_raw_buffer_load_b128(urs, uoff + q * 256, soff, 0));
+        }
       }
     }
-    __syncthreads();
-    const f4* src = a_src(s_v[SB ^ 1], 0);
+    if (TL < 3) {  // after the last step comes the barrier between items, or nothing
+      __syncthreads();
+      const f4* src = a_src(s_v[SB ^ 1], 0);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) a[q] = src[q];
+      for (int q = 0; q < 4; ++q) a[q] = src[q];
+    }
   };
   using C0 = std::integral_constant<int, 0>;
   using C1 = std::integral_constant<int, 1>;
-  step(0, C0{}, std::true_type{});
-  int k = 1;
-  for (; k + 1 < nch; k += 2) {
-    step(k, C1{}, std::false_type{});
-    step(k + 1, C0{}, std::false_type{});
+  using T2 = std::integral_constant<int, 2>;
+  using T3 = std::integral_constant<int, 3>;
+  using Fi = std::true_type;
+  using No = std::false_type;
+  WINO_TS_AT(b, 2);
+  if (!kTail) {
+    step(0, C0{}, Fi{}, C0{});
+    int k = 1;
+    for (; k + 1 < nch; k += 2) {
+      step(k, C1{}, No{}, C0{});
+      step(k + 1, C0{}, No{}, C0{});
+    }
+    if (k < nch) step(k, C1{}, No{}, C0{});
+  } else {
+    // TAILK: nch is even, so the last chunk sits in buffer 1 and the tail steps are one copy
+    // of code on the one path out of the loop.  (With a copy per parity, or per small nch, the
+    // compiler spilled the accumulators where the accumulating paths join; odd chunk counts
+    // run the kernel's TAILK = false form.)  Full steps 0 .. nch - 4, then TAIL 1, 2, 3;
+    // nch = 2 enters at TAIL 2 from zeroed accumulators, the same sums as FIRST's zero operand.
+    if (nch >= 4) {
+      step(0, C0{}, Fi{}, C0{});
+      int k = 1;
+      for (; k + 3 < nch; k += 2) {
+        step(k, C1{}, No{}, C0{});
+        step(k + 1, C0{}, No{}, C0{});
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 24; ++i) acc[i] = f4{0.f, 0.f, 0.f, 0.f};
+    }
+    // (a branch of its own: inside the block above this step cost the PRE form 24 B of scratch)
+    if (nch >= 4) step(nch - 3, C1{}, No{}, C1{});
+    step(nch - 2, C0{}, No{}, T2{});
+    step(nch - 1, C1{}, No{}, T3{});
   }
-  if (k < nch) step(k, C1{}, std::false_type{});
+  WINO_TS_AT(b, 3);
 
   // output transform straight from registers: tile row kq, tiles rg = 0..3 -> output rows
   // oy0 + 2 kq + h, one f4 strip per tile
@@ -1469,6 +1606,7 @@ __device__ __forceinline__ void k16_item24(
         }
       }
     }
+    WINO_TS_AT(b, 4);
     if (stats) {
       merge_stats(lm, lm2, __shfl_xor(lm, 16, 64), __shfl_xor(lm2, 16, 64), 32.f);
       merge_stats(lm, lm2, __shfl_xor(lm, 32, 64), __shfl_xor(lm2, 32, 64), 64.f);
@@ -1479,10 +1617,12 @@ __device__ __forceinline__ void k16_item24(
       }
     }
   }
+  WINO_TS_AT(b, 5);
 }
 
 // the persistent walk of wino_f23_k16_kernel over F(2x4,3x3) items
-template <bool PRE>
+// TAILK: the chunk count per workgroup is even (k16_item24's peeled tail steps)
+template <bool PRE, bool TAILK>
 __global__ __launch_bounds__(512, 1) void wino_f24_k16_kernel(
     const float* __restrict__ x, const float* __restrict__ U, const float* __restrict__ bias,
     const float* __restrict__ skip, const float2* __restrict__ pre, float* __restrict__ y,
@@ -1497,9 +1637,13 @@ __global__ __launch_bounds__(512, 1) void wino_f24_k16_kernel(
     stride = G >> 3;
     end = start + q + (xc < r ? 1u : 0u);
   }
+  Item24Carry carry;
+  carry.tab_n = -1;
+  carry.u_ready = false;
   for (unsigned b = first; b < end; b += stride) {
     if (b != first) __syncthreads();
-    k16_item24<PRE>(b, x, U, bias, skip, pre, y, stats, g, x2);
+    const unsigned nb = b + stride < end ? b + stride : ~0u;
+    k16_item24<PRE, TAILK>(b, nb, x, U, bias, skip, pre, y, stats, g, x2, carry);
   }
 }
 
@@ -1910,12 +2054,11 @@ static int wino_f24_launch(const float* x, const float* x2, int C1, const float*
   hipStream_t st = bpk::as_stream(stream);
   const unsigned kg = k16_grid(items);
   const int remap = (kg % 8 == 0) ? 1 : 0;
-  if (pre)
-    hipLaunchKernelGGL((wino_f24_k16_kernel<true>), dim3(kg), dim3(512), 0, st, x, U, bias, skip,
-                       kpre, y, stats2, gk, remap, x2, (unsigned)items);
-  else
-    hipLaunchKernelGGL((wino_f24_k16_kernel<false>), dim3(kg), dim3(512), 0, st, x, U, bias, skip,
-                       kpre, y, stats2, gk, remap, x2, (unsigned)items);
+  const bool even = (Cin / 16 / std::max(S, 1)) % 2 == 0;  // chunks per workgroup
+  auto kern = pre ? (even ? wino_f24_k16_kernel<true, true> : wino_f24_k16_kernel<true, false>)
+                  : (even ? wino_f24_k16_kernel<false, true> : wino_f24_k16_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3(kg), dim3(512), 0, st, x, U, bias, skip, kpre, y, stats2, gk,
+                     remap, x2, (unsigned)items);
   BPK_LAUNCH_CHECK("conv3x3_wino_f24");
   if (geo) *geo = gk;
   return BPK_OK;

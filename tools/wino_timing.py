@@ -6,8 +6,13 @@ records the 100 MHz wall clock at entry, after its prologue, after its chunk loo
 its epilogue, plus the CU it ran on) and runs the PRE+stats conv of the given shapes.
 Reports per-workgroup phase durations and, per CU, the idle gap between one workgroup's
 end and the next one's start, and how many workgroups were resident on a CU at once.
-Usage: python tools/wino_timing.py [cin cout hw] ...  (default: the 128->128@128 and
+Usage: python tools/wino_timing.py [--f24] [cin cout hw] ...  (default: the 128->128@128 and
 256->256@128 shapes of the NCSN++ mix, B=64)
+
+--f24: the F(2x4,3x3) form (wino_f24_k16_kernel, k16_item24).  Its marks are per item, not per
+workgroup -- entry, first V ready, loop start, loop end, stores issued, item end -- so the
+report is per item: prologue = entry .. loop start, loop, epilogue = loop end .. item end, and
+the per-CU gap is the time from one item's end to the next item's entry on that CU.
 """
 import ctypes
 import os
@@ -22,26 +27,36 @@ LIB = os.environ.get("WINO_TIMING_LIB", os.path.join(REPO, "b-pinn-kalman-filter
 TICK_US = 0.01  # wall_clock64: 100 MHz
 
 
-def run(lib, B, cin, cout, hw, dev):
+def run(lib, B, cin, cout, hw, dev, f24=False):
     g = torch.Generator(device=dev).manual_seed(0)
     x = torch.randn(B, cin, hw, hw, device=dev, generator=g)
     w = torch.randn(cout, cin, 3, 3, device=dev, generator=g) / (3 * cin ** 0.5)
     b = torch.randn(cout, device=dev, generator=g)
     pre = torch.stack([torch.rand(B, cin, device=dev, generator=g) + 0.5,
                        torch.randn(B, cin, device=dev, generator=g) * 0.1], -1).contiguous()
-    nU = lib.bpk_conv3x3_wino_filter_bytes(cin, cout) // 4
+    nU = (lib.bpk_conv3x3_wino_filter24_bytes if f24 else lib.bpk_conv3x3_wino_filter_bytes)(
+        cin, cout) // 4
     U = torch.empty(nU, device=dev)
     y = torch.empty(B, cout, hw, hw, device=dev)
     R = (hw // 8) * (hw // 16)
     part = torch.empty(B, cout, R, 2, device=dev)
     P = ctypes.c_void_p
-    assert lib.bpk_conv3x3_wino_filter_f32(P(w.data_ptr()), P(U.data_ptr()), cin, cout, None) == 0
+    filt = lib.bpk_conv3x3_wino_filter24_f32 if f24 else lib.bpk_conv3x3_wino_filter_f32
+    assert filt(P(w.data_ptr()), P(U.data_ptr()), cin, cout, None) == 0
+    if f24:
+        assert lib.bpk_conv3x3_wino_splitk_bytes(B, cin, cin, cout, hw, hw) == 0, "split-K shape"
 
     def call():
-        rc = lib.bpk_conv3x3_wino_ex_f32(P(x.data_ptr()), None, cin, P(pre.data_ptr()),
-                                         P(U.data_ptr()), P(b.data_ptr()), None,
-                                         ctypes.c_float(1.0), P(y.data_ptr()),
-                                         P(part.data_ptr()), B, cin, cout, hw, hw, None)
+        if f24:
+            rc = lib.bpk_conv3x3_wino_f24_splitk_f32(
+                P(x.data_ptr()), None, cin, P(pre.data_ptr()), P(U.data_ptr()), P(b.data_ptr()),
+                None, ctypes.c_float(1.0), P(y.data_ptr()), P(part.data_ptr()), None, B, cin, cout,
+                hw, hw, None)
+        else:
+            rc = lib.bpk_conv3x3_wino_ex_f32(P(x.data_ptr()), None, cin, P(pre.data_ptr()),
+                                             P(U.data_ptr()), P(b.data_ptr()), None,
+                                             ctypes.c_float(1.0), P(y.data_ptr()),
+                                             P(part.data_ptr()), B, cin, cout, hw, hw, None)
         assert rc == 0, lib.bpk_last_error()
     for _ in range(int(os.environ.get("WINO_TIMING_WARM", "30"))):  # clocks ramp up
         call()
@@ -59,11 +74,15 @@ def run(lib, B, cin, cout, hw, dev):
     cu = np.zeros(nblk, dtype=np.uint32)
     n = lib.bpk_wino_timing_read(ts6.ctypes.data_as(P), cu.ctypes.data_as(P), nblk)
     assert n == nblk, n
-    ts = ts6[:, [0, 3, 4, 5]]
+    ts = ts6[:, [0, 2, 3, 5]] if f24 else ts6[:, [0, 3, 4, 5]]
     ghz = (ts6[:, 7] - ts6[:, 6]) / ((ts6[:, 5] - ts6[:, 0]) * TICK_US * 1e3)
     sub = (ts6[:, 1:4] - ts6[:, 0:3]) * TICK_US
-    print(f"  prologue parts us (mean): loads landed {sub[:, 0].mean():.2f}, patch stores "
-          f"{sub[:, 1].mean():.2f}, first transform {sub[:, 2].mean():.2f}")
+    if f24:
+        print(f"  item parts us (median): entry to first V {np.median(sub[:, 0]):.2f}, stores "
+              f"issued after loop end {np.median((ts6[:, 4] - ts6[:, 3]) * TICK_US):.2f}")
+    else:
+        print(f"  prologue parts us (mean): loads landed {sub[:, 0].mean():.2f}, patch stores "
+              f"{sub[:, 1].mean():.2f}, first transform {sub[:, 2].mean():.2f}")
     t0 = ts[:, 0].min()
     t = (ts - t0) * TICK_US  # us
     pro, loop, epi = t[:, 1] - t[:, 0], t[:, 2] - t[:, 1], t[:, 3] - t[:, 2]
@@ -116,12 +135,15 @@ def main():
     torch.cuda.init()
     lib = ctypes.CDLL(LIB, mode=ctypes.RTLD_GLOBAL)
     lib.bpk_conv3x3_wino_filter_bytes.restype = ctypes.c_int64
+    lib.bpk_conv3x3_wino_filter24_bytes.restype = ctypes.c_int64
+    lib.bpk_conv3x3_wino_splitk_bytes.restype = ctypes.c_int64
     lib.bpk_last_error.restype = ctypes.c_char_p
-    a = [int(v) for v in sys.argv[1:]]
+    f24 = "--f24" in sys.argv[1:]
+    a = [int(v) for v in sys.argv[1:] if v != "--f24"]
     shapes = [tuple(a[i:i + 3]) for i in range(0, len(a), 3)] or [(128, 128, 128), (256, 256, 128),
                                                                   (256, 256, 32)]
     for cin, cout, hw in shapes:
-        run(lib, 64, cin, cout, hw, dev)
+        run(lib, 64, cin, cout, hw, dev, f24)
 
 
 if __name__ == "__main__":
