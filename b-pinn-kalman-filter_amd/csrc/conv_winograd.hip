@@ -9,22 +9,27 @@
 //     M_pos[tile, cout] = sum_cin V_pos[tile, cin] * U_pos[cin, cout]
 // which runs on MFMA with exact f32 products (a k-ordered fma chain).
 //
-// Kernel shape (one workgroup = 4 waves, 256 threads):
-//   * output region: 4 x 8 tiles (8 x 16 pixels) of one image -> M = 32 tiles,
-//     64 output channels (wave w owns couts [16w, 16w + 16));
-//   * K loop over cin in chunks of 8: the 8 x 10 x 18 input patch is loaded to LDS,
-//     each thread transforms one (cin, tile) pair into its 16 V values (LDS), then every
-//     wave issues 16 positions x 2 M-blocks x 2 k-steps = 64 MFMAs 16x16x4 against its
-//     U operands, prefetched from global one chunk ahead;
-//   * accumulators: 16 positions x 2 M-blocks x 4 = 128 f32 per lane; the output
-//     transform is lane-local (all 16 positions of a (tile, cout) sit in one lane), the
-//     result goes through LDS so every global store is a 64-B row segment;
-//   * XCD-aware block order: the cout-blocks of one spatial region are consecutive in
-//     the logical order, which is dealt to one XCD, so they share the input patch in L2.
-// Filter transform U = G g G^T (16 x cin x cout) is a separate, tiny kernel; callers
-// cache U while the weights do not change (sampling).
-// The 16-cin kernel also has an F(2x4, 3x3) form (k16_item24, wino_f24.h): 24 points per 2 x 4
-// tile, 0.75 of the MFMAs for the same conv; the forward convs of the samplers run on it.
+// Every form works on one 8 x 16-pixel region of one image per workgroup, a wave owning 16
+// output channels: the input patch (10 x 18 per cin) goes to LDS, is transformed to V in LDS,
+// and the waves run the MFMAs against U operands prefetched from global memory; the output
+// transform is lane-local and stores straight from registers.  A GroupNorm+SiLU prologue
+// (PRE) needs the per-channel table in LDS: at most kPreMaxCin input channels.  The forms,
+// and when the host (wino_ex, wino_splitk, k16_launch) picks each:
+//   * wino_f23_pipe_kernel -- 8-cin chunks, software-pipelined, 4 waves x 64 couts, or 8
+//     waves x 128 couts for a prologue conv without a residual tail whose padded Cout is a
+//     multiple of 128: the shapes the 16-cin forms do not take (Cin or C1 % 16 != 0, padded
+//     Cout % 128 != 0);
+//   * wino_f23_k16_kernel (k16_item) -- 16-cin chunks, 8 waves x 128 couts, persistent over
+//     the items: padded Cout % 128 == 0 and Cin, C1 % 16 == 0 with an F(2x2) filter (every
+//     backward-data conv, bpk_conv3x3_wino_up2_f32); its PAIR instantiation puts two
+//     8-pixel-wide images side by side in a region (W == 8, CIFAR-10's 8 x 8 level);
+//   * wino_f24_k16_kernel (k16_item24, wino_f24.h) -- the same item as F(2x4, 3x3): 24
+//     points per 2 x 4 tile, 0.75 of the MFMAs; callers that hold a U24 filter ask for it
+//     (bpk_conv3x3_wino_f24_*: the forward convs of the samplers);
+//   * wino_splitk_reduce_kernel -- epilogue of a 16-cin launch split over the input
+//     channels (wino_splits: launches that would leave most CUs idle).
+// The filter transforms U = G g G^T (16 or 24 x cin x cout) are separate, tiny kernels;
+// callers cache U while the weights do not change (sampling).
 #include "bpk_common.h"
 #include "wino_f24.h"
 
@@ -156,12 +161,8 @@ struct WinoGeo {
 };
 
 constexpr int kVS = 20;                  // LDS stride of one (cin, tile) V record (16 + pad)
-constexpr int kOS = kOutRows * kOutCols + 4;  // LDS stride of one staged output channel
-constexpr int kPatchPerThread = (kCK * kPR * kPC + 255) / 256;  // 6
-constexpr int kPreMaxCin = 1024;        // pipelined kernel: GroupNorm affine table in LDS
+constexpr int kPreMaxCin = 1024;        // GroupNorm affine table in LDS
 
-// NB = MFMA N-blocks (16 couts each) per wave: NB = 2 -> 256 accumulator registers, one
-// workgroup per CU; NB = 1 -> 128, two workgroups per CU whose phases interleave.
 // PRE: the conv input is act(GroupNorm(x + b)) given as x and its per-(n, cin) affine form
 // pre[n][cin] = (s, t) (bpk_group_norm_affine_f32): the patch load applies silu(x s + t)
 // (zero padding stays zero), so the normalized tensor is never written to HBM.
@@ -190,13 +191,6 @@ __device__ inline float div_rn(float a, float b, float r) {
   return fmaf(fmaf(-q, b, a), r, q);
 }
 
-// Coalesced stores of one wave's staged output (kWN couts x 8 rows x 16 cols, LDS s_w[co]
-// at stride kOS), with the residual-block tail, and -- stats != nullptr -- the GroupNorm
-// partial statistics of the stored values: stats[n][cout][region] = (mean, M2) of the
-// region's 128 pixels (bpk_group_norm_affine_partials_f32 consumes them, so the next
-// GroupNorm needs no statistics pass over this tensor).  Per iteration the 32 lanes of a
-// half-wave hold one channel's 128 values; the butterfly merge (equal counts) gives every
-// lane the same bits.
 template <int CTRL>
 __device__ inline float dpp_f(float v) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, false));
@@ -208,293 +202,6 @@ __device__ inline void merge_stats(float& m, float& m2, float mo, float m2o, flo
   const float d = mo - m;
   m2 = (m2 + m2o) + d * d * (0.5f * c);
   m = 0.5f * (m + mo);
-}
-
-template <int kWN>
-__device__ inline void store_tile(const float* s_w, const float* __restrict__ skip,
-                                  float* __restrict__ y, float2* __restrict__ stats,
-                                  const WinoGeo& g, int n, int cout_w, int oy0, int ox0, int lane) {
-  if (cout_w >= g.CoutS) return;  // padded couts (wave-uniform: CoutS % 16 == 0)
-  const int64_t plane = (int64_t)g.H * g.W;
-  constexpr int kIt = kWN / 2;
-  float mm[kIt], qq[kIt];
-  auto out_off = [&](int it) {
-    const int q = it * 64 + lane;
-    const int co = q >> 5;                 // 32 float4 per cout (8 rows x 4)
-    const int rem = q & 31;
-    const int row = rem >> 2, c4 = rem & 3;
-    return (int64_t)n * g.CoutS * plane + (int64_t)(cout_w + co) * plane +
-           (int64_t)(oy0 + row) * g.W + ox0 + 4 * c4;
-  };
-  // residual tail: every skip vector of the tile requested before the first is used (one
-  // exposed memory latency, as the 16-cin kernel's epilogue)
-  f4 skv[kIt];
-  if (skip) {
-#pragma unroll
-    for (int it = 0; it < kIt; ++it) skv[it] = *reinterpret_cast<const f4*>(&skip[out_off(it)]);
-  }
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int q = it * 64 + lane;
-    const int co = q >> 5;
-    const int rem = q & 31;
-    const int row = rem >> 2, c4 = rem & 3;
-    f4 v = *reinterpret_cast<const f4*>(&s_w[co * kOS + row * kOutCols + 4 * c4]);
-    const int64_t o = out_off(it);
-    if (skip) {  // residual block tail, same operation order as bpk_residual_rescale_f32
-      const f4 sk = skv[it];
-      v = f4{(sk[0] + v[0]) / g.div, (sk[1] + v[1]) / g.div, (sk[2] + v[2]) / g.div,
-             (sk[3] + v[3]) / g.div};
-    }
-    *reinterpret_cast<f4*>(&y[o]) = v;
-    mm[it] = ((v[0] + v[1]) + (v[2] + v[3])) * 0.25f;
-    float m2 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) m2 = fmaf(v[e] - mm[it], v[e] - mm[it], m2);
-    qq[it] = m2;
-  }
-  if (!stats) return;
-  // 32-lane reductions (one channel per half-wave and iteration), all iterations interleaved:
-  // xor 1, xor 2 (quad_perm), 8-lane and 16-lane mirrors (DPP), then xor 16 (bpermute)
-#pragma unroll
-  for (int it = 0; it < kIt; ++it)
-    merge_stats(mm[it], qq[it], dpp_f<0xB1>(mm[it]), dpp_f<0xB1>(qq[it]), 4.f);
-#pragma unroll
-  for (int it = 0; it < kIt; ++it)
-    merge_stats(mm[it], qq[it], dpp_f<0x4E>(mm[it]), dpp_f<0x4E>(qq[it]), 8.f);
-#pragma unroll
-  for (int it = 0; it < kIt; ++it)
-    merge_stats(mm[it], qq[it], dpp_f<0x141>(mm[it]), dpp_f<0x141>(qq[it]), 16.f);
-#pragma unroll
-  for (int it = 0; it < kIt; ++it)
-    merge_stats(mm[it], qq[it], dpp_f<0x140>(mm[it]), dpp_f<0x140>(qq[it]), 32.f);
-#pragma unroll
-  for (int it = 0; it < kIt; ++it)
-    merge_stats(mm[it], qq[it], __shfl_xor(mm[it], 16, 64), __shfl_xor(qq[it], 16, 64), 64.f);
-  const int R = g.regions_x * g.regions_y;
-  const int region = (oy0 / kOutRows) * g.regions_x + ox0 / kOutCols;
-  if ((lane & 31) == 0) {
-#pragma unroll
-    for (int it = 0; it < kIt; ++it) {
-      const int co = (it * 64 + lane) >> 5;
-      stats[((int64_t)n * g.CoutS + cout_w + co) * R + region] = make_float2(mm[it], qq[it]);
-    }
-  }
-}
-
-template <int NB, bool PRE>
-__global__ __launch_bounds__(256, NB == 1 ? 2 : 1) void wino_f23_kernel(const float* __restrict__ x,
-                                                          const float* __restrict__ U,
-                                                          const float* __restrict__ bias,
-                                                          const float* __restrict__ skip,
-                                                          const float2* __restrict__ pre,
-                                                          float* __restrict__ y,
-                                                          float2* __restrict__ stats, WinoGeo g,
-                                                          int xcd_remap) {
-  __shared__ float2 s_ss[2][kCK];  // PRE: (s, t) of the chunk's input channels
-  // patch [cin][row][col] + a tail that absorbs the writes of out-of-patch slots (so the
-  // stores are branch-free, like the loads)
-  __shared__ float s_patch_raw[kCK * kPR * kPCp + 256];  //  7.1 KB
-  float(*s_patch)[kPR][kPCp] = reinterpret_cast<float(*)[kPR][kPCp]>(s_patch_raw);
-  __shared__ __attribute__((aligned(16))) float s_v[kCK * kM * kVS];  // 20.5 KB
-  __shared__ __attribute__((aligned(16))) float s_out[4 * 16 * NB * kOS];  // 33.8 KB per NB
-
-  constexpr int kWN = 16 * NB;  // couts per wave
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-
-  // logical block index: blocks b and b + 8 share an XCD under round-robin placement,
-  // so consecutive logical blocks (the cout-blocks of one region) read one input patch
-  int64_t nblk = (int64_t)gridDim.x;
-  int64_t b = blockIdx.x;
-  if (xcd_remap) b = (b % 8) * (nblk / 8) + b / 8;
-  const int cb = (int)(b % g.cout_blocks);
-  int64_t r = b / g.cout_blocks;
-  const int rx = (int)(r % g.regions_x);
-  r /= g.regions_x;
-  const int ry = (int)(r % g.regions_y);
-  const int n = (int)(r / g.regions_y);
-  const int oy0 = ry * kOutRows, ox0 = rx * kOutCols;
-  const int cout_w = cb * (4 * kWN) + wave * kWN;  // first cout of this wave
-
-  f4 acc[16][2][NB];
-#pragma unroll
-  for (int p = 0; p < 16; ++p)
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) acc[p][mb][nb] = f4{0.f, 0.f, 0.f, 0.f};
-
-  const int64_t plane = (int64_t)g.H * g.W;
-  const float* xn = x + (int64_t)n * g.Cin * plane;
-  const int kq = lane >> 4, jj = lane & 15;
-
-  // patch element i of this thread: (cin, row, col) of the 8 x 10 x 18 patch
-  float pv[kPatchPerThread];
-  // branch-free: every lane issues every load (out-of-image / tail elements read a valid
-  // in-plane address and are zeroed after), so the outstanding-load count is static and
-  // the compiler's vmcnt waits stay exact -- the prefetch really overlaps the MFMAs
-  // the zero-padding select is applied when the values are stored to LDS (next chunk),
-  // not here: a select right after a load would wait for that load immediately
-  unsigned pmask = 0;
-  auto load_patch = [&](int c0) {
-    pmask = 0;
-#pragma unroll
-    for (int e = 0; e < kPatchPerThread; ++e) {
-      const int i = tid + 256 * e;
-      const bool in_patch = i < kCK * kPR * kPC;
-      const int ii = in_patch ? i : 0;
-      const int c = ii / (kPR * kPC);
-      const int rr = ii - c * (kPR * kPC);
-      const int py = rr / kPC, px = rr - py * kPC;
-      const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
-      const bool inb = in_patch && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W;
-      const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
-      pv[e] = xn[(int64_t)(c0 + c) * plane + (int64_t)cy * g.W + cx];
-      pmask |= inb ? (1u << e) : 0u;
-    }
-  };
-  load_patch(0);
-
-  // B operands: uo[ks][nb][q] = U[c0 + 4ks + kq][cout_w + 16nb + jj][4q..4q+3]; the next
-  // chunk's are loaded right after this chunk's MFMAs have issued, so their latency
-  // overlaps the patch store, the V transform and both barriers of the next chunk
-  f4 uo[2][NB][4];
-  auto load_u = [&](int c0) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        const f4* src = reinterpret_cast<const f4*>(
-            U + ((int64_t)(c0 + 4 * ks + kq) * g.Cout + cout_w + 16 * nb + jj) * 16);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) uo[ks][nb][q] = src[q];
-      }
-  };
-  load_u(0);
-  const float2* pre_n = PRE ? pre + (int64_t)n * g.Cin : nullptr;
-  float2 ss_next = make_float2(1.f, 0.f);
-  if (PRE) {
-    if (tid < kCK) s_ss[0][tid] = pre_n[tid];
-    __syncthreads();
-  }
-
-  for (int c0 = 0; c0 < g.Cin; c0 += kCK) {
-    const int sbuf = (c0 / kCK) & 1;
-    // 1. patch registers -> LDS
-#pragma unroll
-    for (int e = 0; e < kPatchPerThread; ++e) {
-      const int i = tid + 256 * e;
-      const int c = i / (kPR * kPC);
-      const int rr = i - c * (kPR * kPC);
-      const int py = rr / kPC, px = rr - py * kPC;
-      const int dst = i < kCK * kPR * kPC ? (c * kPR + py) * kPCp + px : kCK * kPR * kPCp + tid;
-      float v = pv[e];
-      if (PRE) {
-        const float2 st = s_ss[sbuf][min(c, kCK - 1)];
-        v = silu_f(v * st.x + st.y);
-      }
-      s_patch_raw[dst] = ((pmask >> e) & 1u) ? v : 0.f;
-    }
-    __syncthreads();
-    // 2. V = B^T d B for one (cin, tile) per thread -> s_v[(c * 32 + m) * kVS + pos]
-    {
-      const int c = tid >> 5, m = tid & 31;
-      const int ty = m / kTC, tx = m - ty * kTC;
-      float d[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[i][j] = s_patch[c][2 * ty + i][2 * tx + j];
-      float t[4][4];  // B^T d   (B^T = [[1,0,-1,0],[0,1,1,0],[0,-1,1,0],[0,1,0,-1]])
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        t[0][j] = d[0][j] - d[2][j];
-        t[1][j] = d[1][j] + d[2][j];
-        t[2][j] = d[2][j] - d[1][j];
-        t[3][j] = d[1][j] - d[3][j];
-      }
-      f4* dst = reinterpret_cast<f4*>(&s_v[(c * kM + m) * kVS]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        dst[i] = f4{t[i][0] - t[i][2], t[i][1] + t[i][2], t[i][2] - t[i][1], t[i][1] - t[i][3]};
-    }
-    __syncthreads();
-    // 3. next chunk's patch in flight during the MFMAs
-    // (unconditional: the last chunk re-loads itself, so every iteration issues the same
-    // loads and the compiler's vmcnt bookkeeping across the back edge stays exact)
-    load_patch(min(c0 + kCK, g.Cin - kCK));
-    if (PRE && tid < kCK) ss_next = pre_n[min(c0 + kCK, g.Cin - kCK) + tid];
-    // 4. MFMAs: acc[p][mb][nb] += V_p[mb*16 + i][4ks + k] * U_p[4ks + k][16nb + j]
-    // A operands (16 positions of one (ks, mb) group = 4 x 16 B) are read one group
-    // ahead, so each group's LDS latency hides behind the previous group's MFMAs.
-    {
-      auto a_src = [&](int grp) {  // grp = 2 ks + mb
-        const int ks = grp >> 1, mb = grp & 1;
-        return reinterpret_cast<const f4*>(&s_v[((4 * ks + kq) * kM + mb * 16 + jj) * kVS]);
-      };
-      f4 a_cur[4], a_nxt[4];
-      {
-        const f4* src = a_src(0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a_cur[q] = src[q];
-      }
-#pragma unroll
-      for (int grp = 0; grp < 4; ++grp) {
-        if (grp < 3) {
-          const f4* src = a_src(grp + 1);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) a_nxt[q] = src[q];
-        }
-        const int ks = grp >> 1, mb = grp & 1;
-#pragma unroll
-        for (int p = 0; p < 16; ++p)
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb)
-            acc[p][mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                a_cur[p >> 2][p & 3], uo[ks][nb][p >> 2][p & 3], acc[p][mb][nb], 0, 0, 0);
-        if (grp < 3) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) a_cur[q] = a_nxt[q];
-        }
-        // keep the next group's 4 LDS reads ahead of this group's MFMAs
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 16 * NB, 0);
-      }
-    }
-    load_u(min(c0 + kCK, g.Cin - kCK));
-    if (PRE && tid < kCK) s_ss[sbuf ^ 1][tid] = ss_next;
-    __syncthreads();
-  }
-
-  // 5. output transform (lane-local) -> per-wave LDS staging [cout][8 x 16 pixels]
-  // acc element (mb, nb, reg): tile m = mb*16 + 4*kq + reg, cout = cout_w + 16nb + jj
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    float* so = &s_out[(wave * kWN + 16 * nb + jj) * kOS];
-    const float bv = (bias && cout_w + 16 * nb + jj < g.CoutS) ? bias[cout_w + 16 * nb + jj] : 0.f;
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int m = mb * 16 + 4 * kq + rg;
-        const int ty = m / kTC, tx = m - ty * kTC;
-        float t0[4], t1[4];  // A^T M with A^T = [[1,1,1,0],[0,1,-1,-1]]
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          t0[j] = acc[j][mb][nb][rg] + acc[4 + j][mb][nb][rg] + acc[8 + j][mb][nb][rg];
-          t1[j] = acc[4 + j][mb][nb][rg] - acc[8 + j][mb][nb][rg] - acc[12 + j][mb][nb][rg];
-        }
-        so[(2 * ty) * kOutCols + 2 * tx] = t0[0] + t0[1] + t0[2] + bv;
-        so[(2 * ty) * kOutCols + 2 * tx + 1] = t0[1] - t0[2] - t0[3] + bv;
-        so[(2 * ty + 1) * kOutCols + 2 * tx] = t1[0] + t1[1] + t1[2] + bv;
-        so[(2 * ty + 1) * kOutCols + 2 * tx + 1] = t1[1] - t1[2] - t1[3] + bv;
-      }
-    }
-  }
-  __syncthreads();
-  // 6. coalesced stores: per wave kWN couts x 8 rows x 16 cols = 32 kWN float4
-  store_tile<kWN>(&s_out[wave * kWN * kOS], skip, y, stats, g, n, cout_w, oy0, ox0, lane);
 }
 
 // Per-workgroup phase timestamps (diagnostic build only, -DWINO_TIMING; tools/wino_timing.py):
@@ -523,28 +230,27 @@ __device__ unsigned g_wino_cu[kTsMax];
 #endif
 #define WINO_TS(slot) WINO_TS_AT(blockIdx.x, slot)
 
-// Software-pipelined form (one workgroup per CU, 4 waves x 32 couts = 128 couts, 32 tiles).
-// The serial form above runs store-patch | barrier | transform | barrier | MFMAs per chunk,
-// so a wave's MFMA pipe idles through the transform phase unless a second workgroup
-// happens to be out of phase.  Here the work of three chunks overlaps inside each wave:
+// Software-pipelined 8-cin form (32 tiles, 16 couts per wave).  A serial schedule runs
+// store-patch | barrier | transform | barrier | MFMAs per chunk, so a wave's MFMA pipe idles
+// through the transform phase.  Here the work of three chunks overlaps inside each wave:
 // while the MFMAs of chunk k read V(k) from one LDS buffer, the same wave transforms
 // patch(k+1) (already in LDS) into the other V buffer, stores patch(k+2) (in registers)
-// into the free patch buffer and issues the global loads of patch(k+3) and of U(k+1) into
-// a second register set -- one barrier per chunk.  The VALU / LDS work (~70 instructions
-// per chunk) fills MFMA issue gaps (128 MFMAs of 32 cycles per chunk per wave).
+// into the free patch buffer and issues the global loads of patch(k+3) and of U(k+1) --
+// one barrier per chunk.  The VALU / LDS work (~70
+// instructions per chunk) fills MFMA issue gaps (64 MFMAs of 32 cycles per chunk per wave).
 // WG = waves per workgroup: 4 (64 couts, two workgroups per CU) or 8 (128 couts, one
-// workgroup per CU, NB = 1): the eight waves share one patch / V stream, so the GroupNorm+SiLU
-// patch stores (4 channels per thread instead of 8: half the SiLU work per SIMD per MFMA of the
-// two-workgroup form).
+// workgroup per CU): the eight waves share one patch / V stream, so the GroupNorm+SiLU
+// patch stores take 4 channels per thread instead of 8 (half the SiLU work per SIMD per MFMA
+// of the two-workgroup form).
 // TAIL (nch = Cin / 8 even and >= 4): the last three chunks are peeled so they skip the side
 // work of chunks that do not exist (patch loads / stores, the V transform and the filter
 // prefetch past the last chunk, and the last barrier) instead of redoing the last chunk's.
-template <int NB, bool PRE, int WG = 4, bool TAIL = false>
-__global__ __launch_bounds__(64 * WG, WG == 8 ? 1 : (NB == 1 ? 2 : 1)) void wino_f23_pipe_kernel(
+template <bool PRE, int WG = 4, bool TAIL = false>
+__global__ __launch_bounds__(64 * WG, WG == 8 ? 1 : 2) void wino_f23_pipe_kernel(
     const float* __restrict__ x, const float* __restrict__ U, const float* __restrict__ bias,
     const float* __restrict__ skip, const float2* __restrict__ pre, float* __restrict__ y,
     float2* __restrict__ stats, WinoGeo g, int xcd_remap, const float* __restrict__ x2) {
-  constexpr int kWN = 16 * NB;  // couts per wave
+  constexpr int kWN = 16;  // couts per wave
   constexpr int kPatch = kCK * kPR * kPCp;
   __shared__ __attribute__((aligned(16))) float s_patch_raw[2][kPatch];     // 2 x 7.5 KB
   constexpr int kVBuf = kCK * kM * kVS;                                      // 20.5 KB
@@ -564,7 +270,6 @@ __global__ __launch_bounds__(64 * WG, WG == 8 ? 1 : (NB == 1 ? 2 : 1)) void wino
   const int n = (int)udivmod(r, (unsigned)g.regions_y, ry);
   const int oy0 = (int)ry * kOutRows, ox0 = (int)rx * kOutCols;
   const int cout_w = (int)cb * (WG * kWN) + wave * kWN;
-  static_assert(WG == 4 || (WG == 8 && NB == 1), "8-wave form: NB = 1");
   // 8 waves: waves 0-3 stage channels 0-3 of a chunk and transform V, waves 4-7 stage
   // channels 4-7 (wave-uniform, in SGPRs).  Every wave transforms (waves w and w + 4 write the
   // same V records, identical values): a wave-uniform branch around the transform, or waves
@@ -574,7 +279,7 @@ __global__ __launch_bounds__(64 * WG, WG == 8 ? 1 : (NB == 1 ? 2 : 1)) void wino
 
   // accumulators: the first chunk's k-step 0 MFMAs take an inline-constant zero C operand
   // (no 128 register clears in the prologue)
-  f4 acc[16][2][NB];
+  f4 acc[16][2];
 
   const int64_t plane = (int64_t)g.H * g.W;
   const int C2 = g.Cin - g.C1;
@@ -636,19 +341,17 @@ __global__ __launch_bounds__(64 * WG, WG == 8 ? 1 : (NB == 1 ? 2 : 1)) void wino
     }
   };
   auto store_patch = [&](float* sp, int k) { store_patch_from(pv, sp, k); };
-  // B operands of one k-step half: uo[ks][nb][q] = U[c0 + 4ks + kq][cout_w + 16nb + jj][4q..]
-  f4 uo[2][NB][4];
+  // B operands of one k-step half: uo[ks][q] = U[c0 + 4ks + kq][cout_w + jj][4q..]
+  f4 uo[2][4];
   const int uoff = ((kq * g.Cout + cout_w + jj) * 16) * 4;
   auto load_u = [&](int ks, int k) {
     const int soff = ((min(k, nch - 1) * kCK + 4 * ks) * g.Cout) * 64;
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        using u4 = __attribute__((ext_vector_type(4))) unsigned;
-        const u4 w = __builtin_amdgcn_raw_buffer_load_b128(urs, uoff + nb * 1024 + q * 16, soff, 0);
-        uo[ks][nb][q] = __builtin_bit_cast(f4, w);
-      }
+    for (int q = 0; q < 4; ++q) {
+      using u4 = __attribute__((ext_vector_type(4))) unsigned;
+      const u4 w = __builtin_amdgcn_raw_buffer_load_b128(urs, uoff + q * 16, soff, 0);
+      uo[ks][q] = __builtin_bit_cast(f4, w);
+    }
   };
   // V = B^T d B of one (cin, tile) per thread
   const int tc = (tid & 255) >> 5, tm = tid & 31;
@@ -707,9 +410,9 @@ __global__ __launch_bounds__(64 * WG, WG == 8 ? 1 : (NB == 1 ? 2 : 1)) void wino
   __syncthreads();
 
   // A operands a[q] = V[pos 4q..4q+3] of (ks, mb) = this lane's tile row of one LDS record;
-  // each a[q] / uo[ks][nb][q] register is refilled (next group's A, next chunk's U) right
-  // after the last MFMA that reads it, so A needs 16 registers and U 64, and every load
-  // has most of a group (>= 24 MFMAs) to land
+  // each a[q] / uo[ks][q] register is refilled (next group's A, next chunk's U) right
+  // after the last MFMA that reads it, so A needs 16 registers and U 32, and every load
+  // has most of a group (>= 12 MFMAs) to land
   f4 a[4];
   auto a_src = [&](const float* sv, int grp) {  // grp = 2 ks + mb
     const int ks = grp >> 1, mb = grp & 1;
@@ -742,22 +445,16 @@ __global__ __launch_bounds__(64 * WG, WG == 8 ? 1 : (NB == 1 ? 2 : 1)) void wino
       for (int q = 0; q < 4; ++q) {
 #pragma unroll
         for (int pp = 0; pp < 4; ++pp)
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb)
-            acc[4 * q + pp][mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                a[q][pp], uo[ks][nb][q][pp],
-                (FIRST && ks == 0) ? f4{0.f, 0.f, 0.f, 0.f} : acc[4 * q + pp][mb][nb], 0, 0, 0);
+          acc[4 * q + pp][mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+              a[q][pp], uo[ks][q][pp],
+              (FIRST && ks == 0) ? f4{0.f, 0.f, 0.f, 0.f} : acc[4 * q + pp][mb], 0, 0, 0);
         // refill: A of the next group (the next chunk's group 0 comes after the barrier)
         if (grp < 3) a[q] = a_src(sv, grp + 1)[q];
         if (TM < 3 && mb == 1) {
           const int soff = ((min(k + 1, nch - 1) * kCK + 4 * ks) * g.Cout) * 64;
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb) {
-            using u4 = __attribute__((ext_vector_type(4))) unsigned;
-            const u4 w = __builtin_amdgcn_raw_buffer_load_b128(urs, uoff + nb * 1024 + q * 16,
-                                                               soff, 0);
-            uo[ks][nb][q] = __builtin_bit_cast(f4, w);
-          }
+          using u4 = __attribute__((ext_vector_type(4))) unsigned;
+          const u4 w = __builtin_amdgcn_raw_buffer_load_b128(urs, uoff + q * 16, soff, 0);
+          uo[ks][q] = __builtin_bit_cast(f4, w);
         }
       }
     }
@@ -800,14 +497,15 @@ __global__ __launch_bounds__(64 * WG, WG == 8 ? 1 : (NB == 1 ? 2 : 1)) void wino
   // output transform straight from registers to global memory (no LDS staging, no
   // barrier).  Per M-block a lane holds tiles m = 16 mb + 4 kq + rg, rg = 0..3: tile row
   // 2 mb + kq / 2, tile cols 4 (kq & 1) + rg -- 2 output rows x 8 pixels of channel
-  // cout_w + 16 nb + jj, stored as two 16-B strips per row (lanes kq, kq ^ 1 cover a whole
+  // cout_w + jj, stored as two 16-B strips per row (lanes kq, kq ^ 1 cover a whole
   // 64-B row).  GroupNorm partial statistics: a running Chan merge over the lane's 32
   // values, then the 4 lanes jj + 16 kq (equal counts, symmetric butterfly: same bits).
   const float rdiv = 1.f / g.div;
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    if (cout_w + 16 * nb >= g.CoutS) continue;  // padded couts (wave-uniform: CoutS % 16 == 0)
-    const int co = cout_w + 16 * nb + jj;
+  // (a one-trip loop: written as `if (cout_w < g.CoutS)` the compiler orders the address
+  // arithmetic of the statistics store differently; unmeasured, so the loop stays)
+  for (int once = 0; once < 1; ++once) {
+    if (cout_w >= g.CoutS) continue;  // padded couts (wave-uniform: CoutS % 16 == 0)
+    const int co = cout_w + jj;
     const float bv = bias ? bias[co] : 0.f;
     const int64_t obase = ((int64_t)n * g.CoutS + co) * plane;
     float lm = 0.f, lm2 = 0.f;
@@ -826,8 +524,8 @@ __global__ __launch_bounds__(64 * WG, WG == 8 ? 1 : (NB == 1 ? 2 : 1)) void wino
             float t[4];  // row h of A^T M, A^T = [[1,1,1,0],[0,1,-1,-1]]
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-              t[j] = h == 0 ? acc[j][mb][nb][rg] + acc[4 + j][mb][nb][rg] + acc[8 + j][mb][nb][rg]
-                            : acc[4 + j][mb][nb][rg] - acc[8 + j][mb][nb][rg] - acc[12 + j][mb][nb][rg];
+              t[j] = h == 0 ? acc[j][mb][rg] + acc[4 + j][mb][rg] + acc[8 + j][mb][rg]
+                            : acc[4 + j][mb][rg] - acc[8 + j][mb][rg] - acc[12 + j][mb][rg];
             v[2 * u] = t[0] + t[1] + t[2] + bv;
             v[2 * u + 1] = t[1] - t[2] - t[3] + bv;
           }
@@ -1094,7 +792,7 @@ __device__ __forceinline__ void k16_item(
   if (k < nch) step(k, C1{}, std::false_type{});
   WINO_TS(4);
 
-  // output transform straight from registers (as wino_f23_pipe_kernel, NB = 1).  PAIR: a
+  // output transform straight from registers (as wino_f23_pipe_kernel).  PAIR: a
   // lane's tile columns 4 (kq & 1) + rg all lie in image n + (kq & 1), at x 0..7
   const float rdiv = 1.f / g.div;
   if (cout_w < g.CoutS) {
@@ -1171,7 +869,7 @@ __device__ __forceinline__ void k16_item(
   WINO_TS(5);
 }
 
-// Persistent form (round 6): gridDim.x workgroups (one per CU, k16_grid) walk the items, so the
+// Persistent form (round 6): gridDim.x workgroups (one per CU, k16_launch) walk the items, so the
 // dispatcher's workgroup turnaround (~1 us between one workgroup's exit and the next one's start
 // on a CU, the round-4 timeline) is paid once per CU instead of once per item.  With xcd_remap
 // the workgroups sharing an XCD (w, w + 8, ...: blocks are dealt round-robin over the 8 XCDs)
@@ -1217,36 +915,21 @@ __global__ __launch_bounds__(512, 1) void wino_f23_k16_kernel(
 //   * U operands: uo[2][6] f4, one f4 per 4 MFMAs, refilled two k-steps ahead right after use;
 //     U24 is laid out per 16-cout group and fragment so that a wave's load is 4 x 256 B.
 // LDS: 2 x 15 KB patches + 2 x 28 KB V + the GroupNorm table (8 KB) = 94 KB.
+// The item boundary (prologue, last steps) is kept short; none of this changes an operand or
+// the order of an accumulation (measurements: profiles/r09_wino_boundary/):
+//   * the prologue issues the GroupNorm table load first, then patch(0), then the rest, so the
+//     first patch store waits for those two only (loads return in issue order); patch(1) is
+//     activated after V(0) is written;
+//   * the table in LDS is reloaded only when the image changes (Item24Carry::tab_n);
+//   * TAILK, which the host picks for even chunk counts (every conv of the nets): steps
+//     nch-3 .. nch-1 are peeled (TL 1..3) without the loads, patch stores, transform and filter
+//     refills of chunks that do not exist; odd counts keep the full-step schedule;
+//   * TAILK: the filter refills of the last step's k-steps 2 and 3 fetch k-steps 0 and 1 of
+//     this slice's first chunk again, and the prologue of the workgroup's next item loads no
+//     filter when that item has the same cout block and split-K slice (a scalar test, once per
+//     item: Item24Carry::u_ready).
 constexpr int kM24 = 16;   // tiles per region
 constexpr int kVS24 = 28;  // LDS stride of one (cin, tile) V record (24 + pad)
-
-// The item boundary (prologue, last steps, epilogue) of k16_item24, one switch per part; a
-// part set to 0 compiles the earlier form (A/B builds, tools/build_variant.sh).  No part
-// changes an operand or the order of an accumulation.
-//   WINO_F24_PRO_ORDER  the prologue issues the GroupNorm table load first, then patch(0), then
-//                       the rest, so the first patch store waits for those two only (loads
-//                       return in issue order); patch(1) is activated after V(0) is written
-//   WINO_F24_TAIL       steps nch-3 .. nch-1 are peeled (TAIL 1..3) without the loads, patch
-//                       stores, transform and filter refills of chunks that do not exist; in the
-//                       TAILK instantiation, which the host picks for even chunk counts (every
-//                       conv of the nets): odd counts keep the full-step schedule
-//   WINO_F24_UNEXT      needs TAIL: the filter refills of the last step's k-steps 2 and 3 fetch
-//                       k-steps 0 and 1 of this slice's first chunk again; the prologue of the
-//                       workgroup's next item loads no filter when that item has the same
-//                       cout block and split-K slice (a scalar test, once per item)
-//   WINO_F24_KEEP_TAB   the GroupNorm table in LDS is reloaded only when the image changes
-#ifndef WINO_F24_PRO_ORDER
-#define WINO_F24_PRO_ORDER 1
-#endif
-#ifndef WINO_F24_TAIL
-#define WINO_F24_TAIL 1
-#endif
-#ifndef WINO_F24_UNEXT
-#define WINO_F24_UNEXT 1
-#endif
-#ifndef WINO_F24_KEEP_TAB
-#define WINO_F24_KEEP_TAB 1
-#endif
 
 // What one workgroup carries from item to item of its walk: the image whose table is in LDS
 // and, when `u_ready`, the first two filter k-steps of the coming item in `uo`.
@@ -1262,8 +945,6 @@ __device__ __forceinline__ void k16_item24(
     const float* __restrict__ bias, const float* __restrict__ skip,
     const float2* __restrict__ pre, float* __restrict__ y, float2* __restrict__ stats,
     const WinoGeo& g, const float* __restrict__ x2, Item24Carry& carry) {
-  constexpr bool kOrder = WINO_F24_PRO_ORDER != 0, kTail = WINO_F24_TAIL != 0 && TAILK;
-  constexpr bool kUNext = kTail && WINO_F24_UNEXT != 0, kKeepTab = WINO_F24_KEEP_TAB != 0;
   constexpr int kOob = (int)0x80000000u;  // buffer offset past every tensor: the load returns 0
                                           // and fetches nothing
   constexpr int CK = 16;
@@ -1288,7 +969,7 @@ __device__ __forceinline__ void k16_item24(
   WINO_TS_AT(b, 0);
   // does the workgroup's next item (nb, ~0u = none) read the same filter slice as this one?
   bool u_next = false;
-  if (kUNext && nb != ~0u) {
+  if (TAILK && nb != ~0u) {
     unsigned cb2, t2;
     unsigned r2 = udivmod(nb, (unsigned)g.cout_blocks, cb2);
     r2 = udivmod(r2, (unsigned)g.regions_x, t2);
@@ -1330,7 +1011,7 @@ __device__ __forceinline__ void k16_item24(
     pdst = py * kPCp + px + ph * 8 * (kPR * kPCp);
   }
   float pv[8];
-  // guard (the prologue of TAIL builds): a chunk past the last is requested out of range, which
+  // guard (the prologue of the TAILK form): a chunk past the last is requested out of range, which
   // fetches nothing and keeps the number of loads in flight the same for every nch
   auto load_patch_part = [&](float* dst, int k, int c0, int cn, bool guard = false) {
     const int cc = (kb + min(k, nch - 1)) * CK;
@@ -1402,11 +1083,11 @@ __device__ __forceinline__ void k16_item24(
   };
 
   // prologue: V(0) in s_v[0], patch(1) in s_patch[1], patch(2) and U(0) in flight
-  const bool tab_load = PRE && !(kKeepTab && carry.tab_n == n);
-  const bool u_have = kUNext && carry.u_ready;  // uo[0], uo[1] came with the previous item
+  const bool tab_load = PRE && carry.tab_n != n;
+  const bool u_have = TAILK && carry.u_ready;  // uo[0], uo[1] came with the previous item
   carry.tab_n = n;
   carry.u_ready = u_next;
-  if (kOrder) {
+  {
     // loads return in issue order: the table and patch(0), which the first stores need, go
     // first and the filter (98 KB per workgroup) last
     float pv0[8], pv1[8];
@@ -1418,8 +1099,8 @@ __device__ __forceinline__ void k16_item24(
     __builtin_amdgcn_sched_barrier(0);
     load_patch_part(pv0, 0, 0, 8);
     __builtin_amdgcn_sched_barrier(0);
-    load_patch_part(pv1, 1, 0, 8, kTail);
-    load_patch_part(pv, 2, 0, 8, kTail);
+    load_patch_part(pv1, 1, 0, 8, TAILK);
+    load_patch_part(pv, 2, 0, 8, TAILK);
     // the filter only where the previous item did not fetch it: in place, under a branch, so
     // that no copy of uo (a wait for every load) is needed where the two cases join; the wait
     // for patch(0) below is exact for the common case, the one without these loads
@@ -1438,25 +1119,7 @@ __device__ __forceinline__ void k16_item24(
     __syncthreads();
     read_d(s_patch_raw[0]);
     write_v(s_v[0]);
-    if (!kTail || nch > 1) store_patch_part(pv1, s_patch_raw[1], 1, 0, 8);  // for step 0
-  } else {
-    float pv0[8], pv1[8];
-    load_patch_part(pv0, 0, 0, 8);
-    load_patch_part(pv1, 1, 0, 8, kTail);
-    load_patch_part(pv, 2, 0, 8, kTail);
-    if (!u_have) {
-      load_u(0, 0, 0);
-      load_u(1, 0, 1);
-    }
-    if (tab_load) {
-      for (int c = tid; c < g.Cin; c += 512) s_ss[c] = pre_n[c];
-      __syncthreads();
-    }
-    store_patch_part(pv0, s_patch_raw[0], 0, 0, 8);
-    if (!kTail || nch > 1) store_patch_part(pv1, s_patch_raw[1], 1, 0, 8);
-    __syncthreads();
-    read_d(s_patch_raw[0]);
-    write_v(s_v[0]);
+    if (!TAILK || nch > 1) store_patch_part(pv1, s_patch_raw[1], 1, 0, 8);  // for step 0
   }
   __syncthreads();
   WINO_TS_AT(b, 1);
@@ -1473,7 +1136,7 @@ __device__ __forceinline__ void k16_item24(
 #pragma unroll
     for (int q = 0; q < 4; ++q) a[q] = src[q];
   }
-  // TL (TAIL builds): 0 = a full step; 1 / 2 / 3 = step nch - 3 / nch - 2 / nch - 1, which has
+  // TL (TAILK): 0 = a full step; 1 / 2 / 3 = step nch - 3 / nch - 2 / nch - 1, which has
   // no patch(k+3) to load / nor a patch(k+2) to store / nor any chunk k + 1
   auto step = [&](int k, auto sb_c, auto first_c, auto tail_c) __attribute__((always_inline)) {
     constexpr int SB = decltype(sb_c)::value;
@@ -1504,7 +1167,7 @@ __device__ __forceinline__ void k16_item24(
         // k-step ks + 2 of this chunk, or ks - 2 of the next; after the last chunk (UNEXT) of
         // this slice's first chunk again, which is what the workgroup's next item starts with
         // when u_next (otherwise 98 KB read for nothing, once or twice per workgroup and launch)
-        if (ks < 2 || TL < 3 || kUNext) {
+        if (ks < 2 || TL < 3 || TAILK) {
           const int soff = ks < 2 ? u_soff(k, ks + 2)
                                   : (TL < 3 ? u_soff(k + 1, ks - 2) : u_soff0[ks - 2]);
           uo[ks & 1][q] = __builtin_bit_cast(
@@ -1526,7 +1189,7 @@ __device__ __forceinline__ void k16_item24(
   using Fi = std::true_type;
   using No = std::false_type;
   WINO_TS_AT(b, 2);
-  if (!kTail) {
+  if (!TAILK) {
     step(0, C0{}, Fi{}, C0{});
     int k = 1;
     for (; k + 1 < nch; k += 2) {
@@ -1650,7 +1313,8 @@ __global__ __launch_bounds__(512, 1) void wino_f24_k16_kernel(
 // Split-K epilogue: y = sum_s part[s] + bias, or (skip + that) / div, and the GroupNorm partial
 // statistics of the stored values, as the 16-cin kernel's own epilogue (the partial slabs are
 // summed in a fixed order: deterministic).  One workgroup = 8 channels x one 8 x 16 region of
-// one image; a half-wave holds one channel's 128 values (the store_tile mapping).
+// one image; a half-wave holds one channel's 128 values (8 rows x 4 float4), reduced over its
+// 32 lanes by a butterfly of equal-count merges that gives every lane the same bits.
 __global__ __launch_bounds__(256) void wino_splitk_reduce_kernel(
     const float* __restrict__ part, int S, const float* __restrict__ bias,
     const float* __restrict__ skip, float* __restrict__ y, float2* __restrict__ stats,
@@ -1701,30 +1365,33 @@ __global__ __launch_bounds__(256) void wino_splitk_reduce_kernel(
 
 static int cout_padded(int Cout) { return (Cout + 63) / 64 * 64; }
 
-// grid of the persistent 16-cin kernel: one workgroup per CU (its launch bound), at most one
-// per item; WINO_PERSIST=0 builds launch one workgroup per item (the round-5 form, for A/B)
-#ifndef WINO_PERSIST
-#define WINO_PERSIST 1
-#endif
-static unsigned k16_grid(int64_t items) {
+static int cu_count() {
   static const int cus = [] {
     int dev = 0, n = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n > 0 ? n : 256;
   }();
-  return (unsigned)(WINO_PERSIST ? std::min<int64_t>(items, cus) : items);
+  return cus;
 }
+
+// ---- filter transforms: U (16 floats per (cin, cout)) and U24 (24, k16_item24) ----------------
 
 extern "C" int64_t bpk_conv3x3_wino_filter_bytes(int Cin, int Cout) {
   return (int64_t)16 * Cin * cout_padded(Cout) * (int64_t)sizeof(float);
 }
 
-static int wino_filter(const float* weight, float* U, int Cin, int Cout, int ft,
-                       void* stream) {
+extern "C" int64_t bpk_conv3x3_wino_filter24_bytes(int Cin, int Cout) {
+  return (int64_t)24 * Cin * cout_padded(Cout) * (int64_t)sizeof(float);
+}
+
+using FilterKernel = void (*)(const float*, float*, int, int, int, int);
+
+static int wino_filter(FilterKernel kern, const float* weight, float* U, int Cin, int Cout,
+                       int ft, void* stream) {
   BPK_REQUIRE(Cin > 0 && Cout > 0, "conv3x3_wino_filter: bad channels %d -> %d", Cin, Cout);
   const int64_t total = (int64_t)Cin * cout_padded(Cout);
-  hipLaunchKernelGGL(wino_filter_kernel, dim3((unsigned)std::min<int64_t>(bpk::ceil_div(total, 256), 4096)),
+  hipLaunchKernelGGL(kern, dim3((unsigned)std::min<int64_t>(bpk::ceil_div(total, 256), 4096)),
                      dim3(256), 0, bpk::as_stream(stream), weight, U, Cin, Cout,
                      cout_padded(Cout), ft);
   BPK_LAUNCH_CHECK("conv3x3_wino_filter");
@@ -1733,12 +1400,22 @@ static int wino_filter(const float* weight, float* U, int Cin, int Cout, int ft,
 
 extern "C" int bpk_conv3x3_wino_filter_f32(const float* weight, float* U, int Cin, int Cout,
                                            void* stream) {
-  return wino_filter(weight, U, Cin, Cout, 0, stream);
+  return wino_filter(wino_filter_kernel, weight, U, Cin, Cout, 0, stream);
 }
 
 extern "C" int bpk_conv3x3_wino_filter_ft_f32(const float* weight, float* U, int Cin, int Cout,
                                               void* stream) {
-  return wino_filter(weight, U, Cin, Cout, 1, stream);
+  return wino_filter(wino_filter_kernel, weight, U, Cin, Cout, 1, stream);
+}
+
+extern "C" int bpk_conv3x3_wino_filter24_f32(const float* weight, float* U, int Cin, int Cout,
+                                             void* stream) {
+  return wino_filter(wino_filter24_kernel, weight, U, Cin, Cout, 0, stream);
+}
+
+extern "C" int bpk_conv3x3_wino_filter24_ft_f32(const float* weight, float* U, int Cin, int Cout,
+                                                void* stream) {
+  return wino_filter(wino_filter24_kernel, weight, U, Cin, Cout, 1, stream);
 }
 
 extern "C" int bpk_conv3x3_wino_filter_batch_f32(const int64_t* jobs, int n, int max_elems,
@@ -1752,44 +1429,7 @@ extern "C" int bpk_conv3x3_wino_filter_batch_f32(const int64_t* jobs, int n, int
   return BPK_OK;
 }
 
-// The PAIR form of the 16-cin kernel (8-pixel-wide images, two per region): one source, no
-// GroupNorm statistics, N even; a GroupNorm prologue needs both images' tables in LDS.
-static bool wino_pair_ok(int N, int Cin, int Cout, int H, int W) {
-  return N > 0 && N % 2 == 0 && W == 8 && H > 0 && H % kOutRows == 0 && Cin % 16 == 0 &&
-         Cout % 16 == 0 && cout_padded(Cout) % 128 == 0;
-}
-
-extern "C" int bpk_conv3x3_wino_pair_supported(int N, int Cin, int Cout, int H, int W) {
-  return wino_pair_ok(N, Cin, Cout, H, W);
-}
-
-static int wino_pair_launch(const float* x, const float* pre, const float* U, const float* bias,
-                            const float* skip, float div, float* y, int N, int Cin, int Cout,
-                            int H, int W, int S, void* stream) {
-  BPK_REQUIRE(wino_pair_ok(N, Cin, Cout, H, W),
-              "conv3x3_wino pair form: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d (need "
-              "W == 8, N even, H %% 8, Cin %% 16, Cout %% 128 == 0)", N, Cin, Cout, H, W);
-  BPK_REQUIRE(!pre || 2 * Cin <= kPreMaxCin, "conv3x3_wino pair form: GroupNorm prologue over "
-              "%d > %d channels", Cin, kPreMaxCin / 2);
-  const int CoutP = cout_padded(Cout);
-  WinoGeo gk{N, Cin, CoutP, H, W, 1, H / kOutRows, CoutP / 128, div, Cin, Cout, 0, S, 1};
-  const int64_t items = (int64_t)(N / 2) * gk.regions_y * gk.cout_blocks * S;
-  BPK_REQUIRE(items < (1LL << 31), "conv3x3_wino pair form: grid too large");
-  const float2* kpre = reinterpret_cast<const float2*>(pre);
-  hipStream_t st = bpk::as_stream(stream);
-  const unsigned kg = k16_grid(items);
-  const int remap = (kg % 8 == 0) ? 1 : 0;
-  const float* kb = S > 1 ? nullptr : bias;
-  const float* ks = S > 1 ? nullptr : skip;
-  if (pre)
-    hipLaunchKernelGGL((wino_f23_k16_kernel<true, true>), dim3(kg), dim3(512), 0, st,
-                       x, U, kb, ks, kpre, y, nullptr, gk, remap, nullptr, (unsigned)items);
-  else
-    hipLaunchKernelGGL((wino_f23_k16_kernel<false, true>), dim3(kg), dim3(512), 0, st,
-                       x, U, kb, ks, kpre, y, nullptr, gk, remap, nullptr, (unsigned)items);
-  BPK_LAUNCH_CHECK("conv3x3_wino_pair");
-  return BPK_OK;
-}
+// ---- shapes ------------------------------------------------------------------------------------
 
 extern "C" int bpk_conv3x3_wino_supported(int N, int Cin, int Cout, int H, int W) {
   // Cout % 64 != 0 (multiples of 16): padded to 64 couts, software-pipelined kernel
@@ -1797,313 +1437,163 @@ extern "C" int bpk_conv3x3_wino_supported(int N, int Cin, int Cout, int H, int W
          W % kOutCols == 0;
 }
 
-extern "C" int bpk_conv3x3_wino_ex_f32(const float* x, const float* x2, int C1, const float* pre,
-                                       const float* U, const float* bias, const float* skip,
-                                       float div, float* y, float* stats, int N, int Cin,
-                                       int Cout, int H, int W, void* stream) {
-  float2* stats2 = reinterpret_cast<float2*>(stats);
-  if (!x2) C1 = Cin;
-  if (W == 8 && !bpk_conv3x3_wino_supported(N, Cin, Cout, H, W)) {
-    BPK_REQUIRE(!x2 && !stats, "conv3x3_wino pair form (W == 8): one source, no statistics");
-    return wino_pair_launch(x, pre, U, bias, skip, div, y, N, Cin, Cout, H, W, 1, stream);
+// channel counts the 16-cin items take: 16-cin chunks that do not straddle the two sources,
+// 128-cout blocks
+static bool k16_channels_ok(int Cin, int C1, int Cout) {
+  return Cin % 16 == 0 && C1 % 16 == 0 && cout_padded(Cout) % 128 == 0;
+}
+
+// The PAIR form of the 16-cin kernel (8-pixel-wide images, two per region): one source, no
+// GroupNorm statistics, N even; a GroupNorm prologue needs both images' tables in LDS.
+static bool wino_pair_ok(int N, int Cin, int Cout, int H, int W) {
+  return N > 0 && N % 2 == 0 && W == 8 && H > 0 && H % kOutRows == 0 && Cout % 16 == 0 &&
+         k16_channels_ok(Cin, Cin, Cout);
+}
+
+extern "C" int bpk_conv3x3_wino_pair_supported(int N, int Cin, int Cout, int H, int W) {
+  return wino_pair_ok(N, Cin, Cout, H, W);
+}
+
+extern "C" int bpk_conv3x3_wino_up2_supported(int N, int Cin, int Cout, int H, int W) {
+  return bpk_conv3x3_wino_supported(N, Cin, Cout, H, W) && k16_channels_ok(Cin, Cin, Cout);
+}
+
+extern "C" int bpk_conv3x3_wino_f24_supported(int N, int Cin, int C1, int Cout, int H, int W) {
+  return N > 0 && Cin > 0 && Cin <= kPreMaxCin && C1 > 0 && C1 <= Cin && Cout > 0 &&
+         Cout % 16 == 0 && k16_channels_ok(Cin, C1, Cout) && H > 0 && H % kOutRows == 0 && W > 0 &&
+         W % kOutCols == 0;
+}
+
+// ---- launches ----------------------------------------------------------------------------------
+
+// the operands of one conv call, as the C ABI passes them (x2, pre, bias, skip, stats may be null)
+struct WinoArgs {
+  const float *x, *x2, *pre, *U, *bias, *skip;
+  float *y, *stats;
+  void* stream;
+};
+
+// Geometry of a 16-cin launch: up = 1 reads x at half resolution (WinoGeo::up), S = split-K
+// slices, pair = 1 the PAIR form.  One item = one region x one 128-cout block x one slice.
+static WinoGeo k16_geo(int N, int Cin, int C1, int Cout, int H, int W, float div, int up, int S,
+                       int pair) {
+  const int CoutP = cout_padded(Cout);
+  WinoGeo g{};
+  g.N = N, g.Cin = Cin, g.C1 = C1, g.Cout = CoutP, g.CoutS = Cout, g.H = H, g.W = W;
+  g.regions_x = pair ? 1 : W / kOutCols;
+  g.regions_y = H / kOutRows;
+  g.cout_blocks = CoutP / 128;
+  g.div = div, g.up = up, g.ksplit = S, g.pair = pair;
+  return g;
+}
+
+static int64_t k16_items(const WinoGeo& g) {
+  return (int64_t)(g.pair ? g.N / 2 : g.N) * g.regions_x * g.regions_y * g.cout_blocks * g.ksplit;
+}
+
+using K16Kernel = void (*)(const float*, const float*, const float*, const float*, const float2*,
+                           float*, float2*, WinoGeo, int, const float*, unsigned);
+
+// One launch of a 16-cin kernel over the items of g (the callers have checked the shape): a
+// persistent grid of one workgroup per CU, at most one per item, XCD-ordered when the grid is a
+// multiple of 8.  f24: a.U is a U24 filter (k16_item24), else F(2x2) (k16_item).  With
+// g.ksplit > 1 every slice writes its raw partial slab to a.y: no bias, tail or statistics.
+static int k16_launch(bool f24, const WinoGeo& g, const WinoArgs& a) {
+  const int64_t items = k16_items(g);
+  BPK_REQUIRE(items < (1LL << 31), "conv3x3_wino: grid too large");
+  // [f24][pre][F(2x2): PAIR; F(2x4): TAILK = an even number of chunks per workgroup]
+  static const K16Kernel kKern[2][2][2] = {
+      {{wino_f23_k16_kernel<false, false>, wino_f23_k16_kernel<false, true>},
+       {wino_f23_k16_kernel<true, false>, wino_f23_k16_kernel<true, true>}},
+      {{wino_f24_k16_kernel<false, false>, wino_f24_k16_kernel<false, true>},
+       {wino_f24_k16_kernel<true, false>, wino_f24_k16_kernel<true, true>}}};
+  const bool even = (g.Cin / 16 / g.ksplit) % 2 == 0;
+  const unsigned grid = (unsigned)std::min<int64_t>(items, cu_count());
+  const bool raw = g.ksplit > 1;
+  hipLaunchKernelGGL(kKern[f24][a.pre != nullptr][f24 ? even : g.pair != 0], dim3(grid), dim3(512),
+                     0, bpk::as_stream(a.stream), a.x, a.U, raw ? nullptr : a.bias,
+                     raw ? nullptr : a.skip, reinterpret_cast<const float2*>(a.pre), a.y,
+                     raw ? nullptr : reinterpret_cast<float2*>(a.stats), g, grid % 8 == 0 ? 1 : 0,
+                     a.x2, (unsigned)items);
+  BPK_LAUNCH_CHECK(f24 ? "conv3x3_wino_f24" : "conv3x3_wino_k16");
+  return BPK_OK;
+}
+
+static int wino_f24_check(int N, int Cin, int C1, int Cout, int H, int W) {
+  BPK_REQUIRE(bpk_conv3x3_wino_f24_supported(N, Cin, C1, Cout, H, W),
+              "conv3x3_wino_f24: unsupported shape N=%d Cin=%d (C1=%d) Cout=%d H=%d W=%d (need "
+              "Cin, C1 %% 16, Cout %% 128, H %% 8, W %% 16 == 0, Cin <= %d)", N, Cin, C1, Cout, H,
+              W, kPreMaxCin);
+  return BPK_OK;
+}
+
+static int wino_pair_check(const WinoArgs& a, int N, int Cin, int Cout, int H, int W) {
+  BPK_REQUIRE(!a.x2 && !a.stats, "conv3x3_wino pair form (W == 8): one source, no statistics");
+  BPK_REQUIRE(wino_pair_ok(N, Cin, Cout, H, W),
+              "conv3x3_wino pair form: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d (need "
+              "W == 8, N even, H %% 8, Cin %% 16, Cout %% 128 == 0)", N, Cin, Cout, H, W);
+  BPK_REQUIRE(!a.pre || 2 * Cin <= kPreMaxCin, "conv3x3_wino pair form: GroupNorm prologue over "
+              "%d > %d channels", Cin, kPreMaxCin / 2);
+  return BPK_OK;
+}
+
+using PipeKernel = void (*)(const float*, const float*, const float*, const float*, const float2*,
+                            float*, float2*, WinoGeo, int, const float*);
+
+// F(2x2) conv of one launch: the form by shape (the map at the top of the file)
+static int wino_ex(const WinoArgs& a, int C1, float div, int N, int Cin, int Cout, int H, int W) {
+  if (!a.x2) C1 = Cin;
+  if (W == 8) {
+    const int rc = wino_pair_check(a, N, Cin, Cout, H, W);
+    return rc != BPK_OK ? rc : k16_launch(false, k16_geo(N, Cin, Cin, Cout, H, W, div, 0, 1, 1), a);
   }
   BPK_REQUIRE(C1 > 0 && C1 <= Cin && C1 % kCK == 0,
               "conv3x3_wino: bad channel split C1=%d of Cin=%d", C1, Cin);
   BPK_REQUIRE(bpk_conv3x3_wino_supported(N, Cin, Cout, H, W),
               "conv3x3_wino: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d (need Cin %% 8, "
               "Cout %% 16, H %% 8, W %% 16 == 0)", N, Cin, Cout, H, W);
+  BPK_REQUIRE(!a.pre || Cin <= kPreMaxCin,
+              "conv3x3_wino: GroupNorm prologue over %d > %d input channels (the table in LDS): "
+              "apply it to the input first", Cin, kPreMaxCin);
+  if (k16_channels_ok(Cin, C1, Cout))
+    return k16_launch(false, k16_geo(N, Cin, C1, Cout, H, W, div, 0, 1, 0), a);
   const int CoutP = cout_padded(Cout);
-  // Kernel choice (each form measured against the others on the NCSN++ / DDPM++ shapes;
-  // the rejected variants -- two persistent forms (register- and LDS-DMA-staged), 128-cout
-  // NB = 2 blocks, the 4-wave residual tail -- are gone, numbers in DESIGN.md section 4):
-  //   * wino_f23_k16_kernel: CoutP % 128 == 0 and 16-cin chunks (every NCSN++ conv);
-  //   * wino_f23_pipe_kernel: the other shapes (8-wave / 128-cout form for the GroupNorm
-  //     prologue convs without a residual tail, 4 waves / 64 couts otherwise);
-  //   * wino_f23_kernel: a GroupNorm prologue over more than kPreMaxCin input channels.
-  const bool pipe_ok = !pre || Cin <= kPreMaxCin;
-  BPK_REQUIRE(!x2 || pipe_ok,
-              "conv3x3_wino: a second input source needs the pipelined kernel");
-  BPK_REQUIRE(Cout == CoutP || pipe_ok,
-              "conv3x3_wino: Cout %% 64 != 0 needs the pipelined kernel (Cin <= %d with pre)",
-              kPreMaxCin);
-  if (pipe_ok) {
-    const int wg = (pre && !skip && CoutP % 128 == 0) ? 8 : 4;
-#ifdef WINO_NO_K16  // variant builds only (tools/build_variant.sh): the 8-cin forms everywhere
-    const bool k16 = false;
-#else
-    const bool k16 = CoutP % 128 == 0 && Cin % 16 == 0 && C1 % 16 == 0;
-#endif
-    if (k16) {
-      WinoGeo gk{N, Cin, CoutP, H, W, W / kOutCols, H / kOutRows, CoutP / 128, div, C1, Cout};
-      const int64_t items = (int64_t)N * gk.regions_x * gk.regions_y * gk.cout_blocks;
-      BPK_REQUIRE(items < (1LL << 31), "conv3x3_wino: grid too large");
-      const float2* kpre = reinterpret_cast<const float2*>(pre);
-      hipStream_t kst = bpk::as_stream(stream);
-      const unsigned kg = k16_grid(items);
-      const int kremap = (kg % 8 == 0) ? 1 : 0;
-      if (pre)
-        hipLaunchKernelGGL((wino_f23_k16_kernel<true>), dim3(kg), dim3(512), 0, kst,
-                           x, U, bias, skip, kpre, y, stats2, gk, kremap, x2, (unsigned)items);
-      else
-        hipLaunchKernelGGL((wino_f23_k16_kernel<false>), dim3(kg), dim3(512), 0, kst,
-                           x, U, bias, skip, kpre, y, stats2, gk, kremap, x2, (unsigned)items);
-      BPK_LAUNCH_CHECK("conv3x3_wino_k16");
-      return BPK_OK;
-    }
-    WinoGeo g{N, Cin, CoutP, H, W, W / kOutCols, H / kOutRows, CoutP / (64 * wg / 4), div,
-              C1, Cout};
-    const int64_t blocks = (int64_t)N * g.regions_x * g.regions_y * g.cout_blocks;
-    BPK_REQUIRE(blocks < (1LL << 31), "conv3x3_wino: grid too large");
-    const int remap = (blocks % 8 == 0) ? 1 : 0;
-    const float2* pre2 = reinterpret_cast<const float2*>(pre);
-    hipStream_t st = bpk::as_stream(stream);
-#define WINO_PIPE(NB_, PRE_, TAIL_)                                                           \
-  hipLaunchKernelGGL((wino_f23_pipe_kernel<NB_, PRE_, 4, TAIL_>), dim3((unsigned)blocks), dim3(256), 0, st, \
-                     x, U, bias, skip, pre2, y, stats2, g, remap, x2)
-    const int nch = Cin / kCK;
-    // peeled tail chunks (GroupNorm-prologue form only: the plain form spills with them)
-    const bool tail = pre && nch % 2 == 0 && nch >= 4;
-#define WINO_PIPE8(PRE_, TAIL_)                                                                 \
-  hipLaunchKernelGGL((wino_f23_pipe_kernel<1, PRE_, 8, TAIL_>), dim3((unsigned)blocks), dim3(512), \
-                     0, st, x, U, bias, skip, pre2, y, stats2, g, remap, x2)
-    if (wg == 8) {
-      if (pre) {
-        if (tail) WINO_PIPE8(true, true); else WINO_PIPE8(true, false);
-      } else {
-        WINO_PIPE8(false, false);
-      }
-    } else if (tail) {
-      WINO_PIPE(1, true, true);
-    } else {
-      if (pre) WINO_PIPE(1, true, false); else WINO_PIPE(1, false, false);
-    }
-#undef WINO_PIPE8
-#undef WINO_PIPE
-    BPK_LAUNCH_CHECK("conv3x3_wino_pipe");
-    return BPK_OK;
-  }
-  WinoGeo g{N, Cin, Cout, H, W, W / kOutCols, H / kOutRows, Cout / 64, div, Cin, Cout};
+  const bool wg8 = a.pre && !a.skip && CoutP % 128 == 0;
+  WinoGeo g{};
+  g.N = N, g.Cin = Cin, g.C1 = C1, g.Cout = CoutP, g.CoutS = Cout, g.H = H, g.W = W;
+  g.regions_x = W / kOutCols, g.regions_y = H / kOutRows, g.cout_blocks = CoutP / (wg8 ? 128 : 64);
+  g.div = div;
   const int64_t blocks = (int64_t)N * g.regions_x * g.regions_y * g.cout_blocks;
   BPK_REQUIRE(blocks < (1LL << 31), "conv3x3_wino: grid too large");
-  const int remap = (blocks % 8 == 0) ? 1 : 0;
-  const float2* pre2 = reinterpret_cast<const float2*>(pre);
-  hipStream_t st = bpk::as_stream(stream);
-#define WINO_LAUNCH(NB_, PRE_)                                                                 \
-  hipLaunchKernelGGL((wino_f23_kernel<NB_, PRE_>), dim3((unsigned)blocks), dim3(256), 0, st, x, \
-                     U, bias, skip, pre2, y, stats2, g, remap)
-  if (pre) WINO_LAUNCH(1, true); else WINO_LAUNCH(1, false);
-#undef WINO_LAUNCH
-  BPK_LAUNCH_CHECK("conv3x3_wino");
+  // peeled tail chunks (GroupNorm-prologue form only: the plain form spills with them)
+  const int nch = Cin / kCK;
+  const bool tail = a.pre && nch % 2 == 0 && nch >= 4;
+  // [pre][8 waves][tail]; tail and wg8 imply pre, so the row without it has one kernel that runs
+  static const PipeKernel kPipe[2][2][2] = {
+      {{wino_f23_pipe_kernel<false, 4, false>, wino_f23_pipe_kernel<false, 4, false>},
+       {wino_f23_pipe_kernel<false, 8, false>, wino_f23_pipe_kernel<false, 8, false>}},
+      {{wino_f23_pipe_kernel<true, 4, false>, wino_f23_pipe_kernel<true, 4, true>},
+       {wino_f23_pipe_kernel<true, 8, false>, wino_f23_pipe_kernel<true, 8, true>}}};
+  hipLaunchKernelGGL(kPipe[a.pre != nullptr][wg8][tail], dim3((unsigned)blocks),
+                     dim3(wg8 ? 512 : 256), 0, bpk::as_stream(a.stream), a.x, a.U, a.bias, a.skip,
+                     reinterpret_cast<const float2*>(a.pre), a.y,
+                     reinterpret_cast<float2*>(a.stats), g, blocks % 8 == 0 ? 1 : 0, a.x2);
+  BPK_LAUNCH_CHECK("conv3x3_wino_pipe");
   return BPK_OK;
 }
 
-// Split-K for 16-cin launches that leave most CUs idle (the 32^2 / 16^2 levels at the small
-// per-GPU batches of a batch-sharded run: B = 8 -> 128 / 32 workgroups on 256 CUs): the input
-// channels are split into S slices (S a power of two, at least 2 chunks per slice), so that
-// items x S is at most one workgroup per CU, then a reduce kernel applies the epilogue.
-static int wino_splits(int N, int Cin, int C1, int Cout, int H, int W) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  const int CoutP = cout_padded(Cout);
-  const bool pair = W == 8 && C1 == Cin && wino_pair_ok(N, Cin, Cout, H, W);
-  if (!pair && (!bpk_conv3x3_wino_supported(N, Cin, Cout, H, W) || CoutP % 128 || Cin % 16 ||
-                C1 % 16))
-    return 1;
-  const int64_t items = pair ? (int64_t)(N / 2) * (H / kOutRows) * (CoutP / 128)
-                             : (int64_t)N * (H / kOutRows) * (W / kOutCols) * (CoutP / 128);
-  const int nch = Cin / 16;
-  int S = 1;
-  while (items * S * 2 <= cus && nch % (2 * S) == 0 && nch / (2 * S) >= 2) S *= 2;
-  return S;
-}
-
-extern "C" int64_t bpk_conv3x3_wino_splitk_bytes(int N, int Cin, int C1, int Cout, int H, int W) {
-  const int S = wino_splits(N, Cin, C1, Cout, H, W);
-  return S > 1 ? (int64_t)S * N * Cout * H * W * (int64_t)sizeof(float) : 0;
-}
-
-extern "C" int bpk_conv3x3_wino_splitk_f32(const float* x, const float* x2, int C1,
-                                           const float* pre, const float* U, const float* bias,
-                                           const float* skip, float div, float* y, float* stats,
-                                           float* workspace, int N, int Cin, int Cout, int H,
-                                           int W, void* stream) {
-  const int S = wino_splits(N, Cin, x2 ? C1 : Cin, Cout, H, W);
-  if (S <= 1)
-    return bpk_conv3x3_wino_ex_f32(x, x2, C1, pre, U, bias, skip, div, y, stats, N, Cin, Cout, H,
-                                   W, stream);
-  if (!x2) C1 = Cin;
-  BPK_REQUIRE(workspace != nullptr, "conv3x3_wino_splitk: workspace is NULL");
-  BPK_REQUIRE(Cout % 16 == 0, "conv3x3_wino_splitk: Cout %% 16 != 0");
-  const int CoutP = cout_padded(Cout);
-  if (W == 8 && !bpk_conv3x3_wino_supported(N, Cin, Cout, H, W)) {
-    BPK_REQUIRE(!x2 && !stats, "conv3x3_wino pair form (W == 8): one source, no statistics");
-    const int rc = wino_pair_launch(x, pre, U, bias, skip, div, workspace, N, Cin, Cout, H, W,
-                                    S, stream);
-    if (rc != BPK_OK) return rc;
-    WinoGeo gr{N, Cin, CoutP, H, W, 1, H / kOutRows, CoutP / 128, div, Cin, Cout, 0, S, 1};
-    const int64_t rblocks = (int64_t)(N / 2) * (Cout / 8) * gr.regions_y;
-    hipLaunchKernelGGL(wino_splitk_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0,
-                       bpk::as_stream(stream), workspace, S, bias, skip, y, nullptr, gr);
-    BPK_LAUNCH_CHECK("conv3x3_wino_pair_splitk_reduce");
-    return BPK_OK;
-  }
-  WinoGeo gk{N, Cin, CoutP, H, W, W / kOutCols, H / kOutRows, CoutP / 128, div, C1, Cout, 0, S};
-  const int64_t items = (int64_t)N * gk.regions_x * gk.regions_y * gk.cout_blocks * S;
-  BPK_REQUIRE(items < (1LL << 31), "conv3x3_wino_splitk: grid too large");
-  const float2* kpre = reinterpret_cast<const float2*>(pre);
-  hipStream_t st = bpk::as_stream(stream);
-  const unsigned kg = k16_grid(items);
-  const int remap = (kg % 8 == 0) ? 1 : 0;
-  if (pre)
-    hipLaunchKernelGGL((wino_f23_k16_kernel<true>), dim3(kg), dim3(512), 0, st, x, U,
-                       nullptr, nullptr, kpre, workspace, nullptr, gk, remap, x2, (unsigned)items);
-  else
-    hipLaunchKernelGGL((wino_f23_k16_kernel<false>), dim3(kg), dim3(512), 0, st, x,
-                       U, nullptr, nullptr, kpre, workspace, nullptr, gk, remap, x2, (unsigned)items);
-  BPK_LAUNCH_CHECK("conv3x3_wino_splitk");
-  const int64_t rblocks = (int64_t)N * (Cout / 8) * gk.regions_x * gk.regions_y;
-  BPK_REQUIRE(Cout % 8 == 0 && rblocks < (1LL << 31), "conv3x3_wino_splitk: reduce grid");
-  hipLaunchKernelGGL(wino_splitk_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0, st,
-                     workspace, S, bias, skip, y, reinterpret_cast<float2*>(stats), gk);
-  BPK_LAUNCH_CHECK("conv3x3_wino_splitk_reduce");
-  return BPK_OK;
-}
-
-extern "C" int bpk_conv3x3_wino_up2_supported(int N, int Cin, int Cout, int H, int W) {
-  return bpk_conv3x3_wino_supported(N, Cin, Cout, H, W) && Cin % 16 == 0 &&
-         cout_padded(Cout) % 128 == 0;
-}
-
-// y = conv3x3(nearest_x2(x)) + bias for x [N, Cin, H/2, W/2], y [N, Cout, H, W]: the 16-cin
-// kernel reads the half-resolution input inside its patch load, so the upsampled tensor is
-// never written (reference layers.py:576-590, Upsample(with_conv=True)).
-extern "C" int bpk_conv3x3_wino_up2_f32(const float* x, const float* U, const float* bias,
-                                        float* y, int N, int Cin, int Cout, int H, int W,
-                                        void* stream) {
-  BPK_REQUIRE(bpk_conv3x3_wino_up2_supported(N, Cin, Cout, H, W),
-              "conv3x3_wino_up2: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d (need Cin %% 16, "
-              "Cout %% 128, H %% 8, W %% 16 == 0)", N, Cin, Cout, H, W);
-  const int CoutP = cout_padded(Cout);
-  WinoGeo gk{N, Cin, CoutP, H, W, W / kOutCols, H / kOutRows, CoutP / 128, 1.0f, Cin, Cout, 1};
-  const int64_t items = (int64_t)N * gk.regions_x * gk.regions_y * gk.cout_blocks;
-  BPK_REQUIRE(items < (1LL << 31), "conv3x3_wino_up2: grid too large");
-  const unsigned kg = k16_grid(items);
-  hipLaunchKernelGGL((wino_f23_k16_kernel<false>), dim3(kg), dim3(512), 0,
-                     bpk::as_stream(stream), x, U, bias, nullptr, nullptr, y, nullptr, gk,
-                     (kg % 8 == 0) ? 1 : 0, nullptr, (unsigned)items);
-  BPK_LAUNCH_CHECK("conv3x3_wino_up2");
-  return BPK_OK;
-}
-
-// ---- F(2x4,3x3) form of the 16-cin kernel (k16_item24): its own filter layout U24 ----------
-// WINO_NO_F24 builds (A/B) report the form unsupported, so every caller stays on F(2x2).
-
-extern "C" int bpk_conv3x3_wino_f24_supported(int N, int Cin, int C1, int Cout, int H, int W) {
-#ifdef WINO_NO_F24
-  return 0;
-#else
-  return N > 0 && Cin > 0 && Cin % 16 == 0 && Cin <= kPreMaxCin && C1 > 0 && C1 <= Cin &&
-         C1 % 16 == 0 && Cout > 0 && Cout % 16 == 0 && cout_padded(Cout) % 128 == 0 && H > 0 &&
-         H % kOutRows == 0 && W > 0 && W % kOutCols == 0;
-#endif
-}
-
-extern "C" int64_t bpk_conv3x3_wino_filter24_bytes(int Cin, int Cout) {
-  return (int64_t)24 * Cin * cout_padded(Cout) * (int64_t)sizeof(float);
-}
-
-static int wino_filter24(const float* weight, float* U, int Cin, int Cout, int ft, void* stream) {
-  BPK_REQUIRE(Cin > 0 && Cout > 0, "conv3x3_wino_filter24: bad channels %d -> %d", Cin, Cout);
-  const int64_t total = (int64_t)Cin * cout_padded(Cout);
-  hipLaunchKernelGGL(wino_filter24_kernel,
-                     dim3((unsigned)std::min<int64_t>(bpk::ceil_div(total, 256), 4096)), dim3(256),
-                     0, bpk::as_stream(stream), weight, U, Cin, Cout, cout_padded(Cout), ft);
-  BPK_LAUNCH_CHECK("conv3x3_wino_filter24");
-  return BPK_OK;
-}
-
-extern "C" int bpk_conv3x3_wino_filter24_f32(const float* weight, float* U, int Cin, int Cout,
-                                             void* stream) {
-  return wino_filter24(weight, U, Cin, Cout, 0, stream);
-}
-
-extern "C" int bpk_conv3x3_wino_filter24_ft_f32(const float* weight, float* U, int Cin, int Cout,
-                                                void* stream) {
-  return wino_filter24(weight, U, Cin, Cout, 1, stream);
-}
-
-// one launch of wino_f24_k16_kernel: S > 1 writes raw partial slabs to y (no epilogue)
-static int wino_f24_launch(const float* x, const float* x2, int C1, const float* pre,
-                           const float* U, const float* bias, const float* skip, float div,
-                           float* y, float* stats, int N, int Cin, int Cout, int H, int W, int up,
-                           int S, WinoGeo* geo, void* stream) {
-  BPK_REQUIRE(bpk_conv3x3_wino_f24_supported(N, Cin, C1, Cout, H, W),
-              "conv3x3_wino_f24: unsupported shape N=%d Cin=%d (C1=%d) Cout=%d H=%d W=%d (need "
-              "Cin, C1 %% 16, Cout %% 128, H %% 8, W %% 16 == 0, Cin <= %d)", N, Cin, C1, Cout, H,
-              W, kPreMaxCin);
-  const int CoutP = cout_padded(Cout);
-  WinoGeo gk{N, Cin, CoutP, H, W, W / kOutCols, H / kOutRows, CoutP / 128, div, C1, Cout, up, S};
-  const int64_t items = (int64_t)N * gk.regions_x * gk.regions_y * gk.cout_blocks * S;
-  BPK_REQUIRE(items < (1LL << 31), "conv3x3_wino_f24: grid too large");
-  const float2* kpre = reinterpret_cast<const float2*>(pre);
-  float2* stats2 = reinterpret_cast<float2*>(stats);
-  hipStream_t st = bpk::as_stream(stream);
-  const unsigned kg = k16_grid(items);
-  const int remap = (kg % 8 == 0) ? 1 : 0;
-  const bool even = (Cin / 16 / std::max(S, 1)) % 2 == 0;  // chunks per workgroup
-  auto kern = pre ? (even ? wino_f24_k16_kernel<true, true> : wino_f24_k16_kernel<true, false>)
-                  : (even ? wino_f24_k16_kernel<false, true> : wino_f24_k16_kernel<false, false>);
-  hipLaunchKernelGGL(kern, dim3(kg), dim3(512), 0, st, x, U, bias, skip, kpre, y, stats2, gk,
-                     remap, x2, (unsigned)items);
-  BPK_LAUNCH_CHECK("conv3x3_wino_f24");
-  if (geo) *geo = gk;
-  return BPK_OK;
-}
-
-// bpk_conv3x3_wino_splitk_f32 with a U24 filter (bpk_conv3x3_wino_filter24_f32): same split
-// rule, workspace (bpk_conv3x3_wino_splitk_bytes) and reduce kernel -- the partial slabs are in
-// the output domain
-extern "C" int bpk_conv3x3_wino_f24_splitk_f32(const float* x, const float* x2, int C1,
-                                               const float* pre, const float* U,
-                                               const float* bias, const float* skip, float div,
-                                               float* y, float* stats, float* workspace, int N,
-                                               int Cin, int Cout, int H, int W, void* stream) {
-  if (!x2) C1 = Cin;
-  const int S = wino_splits(N, Cin, C1, Cout, H, W);
-  if (S <= 1)
-    return wino_f24_launch(x, x2, C1, pre, U, bias, skip, div, y, stats, N, Cin, Cout, H, W, 0, 1,
-                           nullptr, stream);
-  BPK_REQUIRE(workspace != nullptr, "conv3x3_wino_f24_splitk: workspace is NULL");
-  WinoGeo gk;
-  const int rc = wino_f24_launch(x, x2, C1, pre, U, nullptr, nullptr, div, workspace, nullptr, N,
-                                 Cin, Cout, H, W, 0, S, &gk, stream);
-  if (rc != BPK_OK) return rc;
-  const int64_t rblocks = (int64_t)N * (Cout / 8) * gk.regions_x * gk.regions_y;
-  BPK_REQUIRE(rblocks < (1LL << 31), "conv3x3_wino_f24_splitk: reduce grid");
-  hipLaunchKernelGGL(wino_splitk_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0,
-                     bpk::as_stream(stream), workspace, S, bias, skip, y,
-                     reinterpret_cast<float2*>(stats), gk);
-  BPK_LAUNCH_CHECK("conv3x3_wino_f24_splitk_reduce");
-  return BPK_OK;
-}
-
-// bpk_conv3x3_wino_up2_f32 with a U24 filter
-extern "C" int bpk_conv3x3_wino_f24_up2_f32(const float* x, const float* U, const float* bias,
-                                            float* y, int N, int Cin, int Cout, int H, int W,
-                                            void* stream) {
-  return wino_f24_launch(x, nullptr, Cin, nullptr, U, bias, nullptr, 1.0f, y, nullptr, N, Cin,
-                         Cout, H, W, 1, 1, nullptr, stream);
+extern "C" int bpk_conv3x3_wino_ex_f32(const float* x, const float* x2, int C1, const float* pre,
+                                       const float* U, const float* bias, const float* skip,
+                                       float div, float* y, float* stats, int N, int Cin,
+                                       int Cout, int H, int W, void* stream) {
+  return wino_ex({x, x2, pre, U, bias, skip, y, stats, stream}, C1, div, N, Cin, Cout, H, W);
 }
 
 extern "C" int bpk_conv3x3_wino_pre_f32(const float* x, const float* pre, const float* U,
                                         const float* bias, const float* skip, float div, float* y,
                                         int N, int Cin, int Cout, int H, int W, void* stream) {
-  return bpk_conv3x3_wino_ex_f32(x, nullptr, Cin, pre, U, bias, skip, div, y, nullptr, N, Cin,
-                                 Cout, H, W, stream);
+  return wino_ex({x, nullptr, pre, U, bias, skip, y, nullptr, stream}, Cin, div, N, Cin, Cout, H,
+                 W);
 }
 
 extern "C" int bpk_conv3x3_wino_residual_f32(const float* x, const float* U, const float* bias,
@@ -2116,6 +1606,101 @@ extern "C" int bpk_conv3x3_wino_f32(const float* x, const float* U, const float*
                                     int N, int Cin, int Cout, int H, int W, void* stream) {
   return bpk_conv3x3_wino_pre_f32(x, nullptr, U, bias, nullptr, 1.0f, y, N, Cin, Cout, H, W,
                                   stream);
+}
+
+// y = conv3x3(nearest_x2(x)) + bias for x [N, Cin, H/2, W/2], y [N, Cout, H, W]: the 16-cin
+// kernel reads the half-resolution input inside its patch load, so the upsampled tensor is
+// never written (reference layers.py:576-590, Upsample(with_conv=True)).
+extern "C" int bpk_conv3x3_wino_up2_f32(const float* x, const float* U, const float* bias,
+                                        float* y, int N, int Cin, int Cout, int H, int W,
+                                        void* stream) {
+  BPK_REQUIRE(bpk_conv3x3_wino_up2_supported(N, Cin, Cout, H, W),
+              "conv3x3_wino_up2: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d (need Cin %% 16, "
+              "Cout %% 128, H %% 8, W %% 16 == 0)", N, Cin, Cout, H, W);
+  return k16_launch(false, k16_geo(N, Cin, Cin, Cout, H, W, 1.0f, 1, 1, 0),
+                    {x, nullptr, nullptr, U, bias, nullptr, y, nullptr, stream});
+}
+
+// bpk_conv3x3_wino_up2_f32 with a U24 filter
+extern "C" int bpk_conv3x3_wino_f24_up2_f32(const float* x, const float* U, const float* bias,
+                                            float* y, int N, int Cin, int Cout, int H, int W,
+                                            void* stream) {
+  const int rc = wino_f24_check(N, Cin, Cin, Cout, H, W);
+  if (rc != BPK_OK) return rc;
+  return k16_launch(true, k16_geo(N, Cin, Cin, Cout, H, W, 1.0f, 1, 1, 0),
+                    {x, nullptr, nullptr, U, bias, nullptr, y, nullptr, stream});
+}
+
+// Split-K for 16-cin launches that leave most CUs idle (the 32^2 / 16^2 levels at the small
+// per-GPU batches of a batch-sharded run: B = 8 -> 128 / 32 workgroups on 256 CUs): the input
+// channels are split into S slices (S a power of two, at least 2 chunks per slice), so that
+// items x S is at most one workgroup per CU, then a reduce kernel applies the epilogue.
+static int wino_splits(int N, int Cin, int C1, int Cout, int H, int W) {
+  const bool pair = W == 8 && C1 == Cin && wino_pair_ok(N, Cin, Cout, H, W);
+  if (!pair && !(bpk_conv3x3_wino_supported(N, Cin, Cout, H, W) && k16_channels_ok(Cin, C1, Cout)))
+    return 1;
+  const int64_t items = k16_items(k16_geo(N, Cin, C1, Cout, H, W, 1.0f, 0, 1, pair));
+  const int nch = Cin / 16;
+  int S = 1;
+  while (items * S * 2 <= cu_count() && nch % (2 * S) == 0 && nch / (2 * S) >= 2) S *= 2;
+  return S;
+}
+
+extern "C" int64_t bpk_conv3x3_wino_splitk_bytes(int N, int Cin, int C1, int Cout, int H, int W) {
+  const int S = wino_splits(N, Cin, C1, Cout, H, W);
+  return S > 1 ? (int64_t)S * N * Cout * H * W * (int64_t)sizeof(float) : 0;
+}
+
+// split rule -> launch -> reduce; S == 1 is the plain launch.  The partial slabs are in the
+// output domain, so both filter forms share the workspace size and the reduce kernel.
+static int wino_splitk(bool f24, const WinoArgs& a, int C1, float div, float* workspace, int N,
+                       int Cin, int Cout, int H, int W) {
+  if (!a.x2) C1 = Cin;
+  if (f24) {
+    const int rc = wino_f24_check(N, Cin, C1, Cout, H, W);
+    if (rc != BPK_OK) return rc;
+  }
+  const int S = wino_splits(N, Cin, C1, Cout, H, W);
+  if (S <= 1)
+    return f24 ? k16_launch(true, k16_geo(N, Cin, C1, Cout, H, W, div, 0, 1, 0), a)
+               : wino_ex(a, C1, div, N, Cin, Cout, H, W);
+  BPK_REQUIRE(workspace != nullptr, "conv3x3_wino_splitk: workspace is NULL");
+  const bool pair = W == 8;  // S > 1: wino_splits has checked the shape of either form
+  if (pair) {
+    const int rc = wino_pair_check(a, N, Cin, Cout, H, W);
+    if (rc != BPK_OK) return rc;
+  }
+  const WinoGeo g = k16_geo(N, Cin, C1, Cout, H, W, div, 0, S, pair);
+  WinoArgs part = a;
+  part.y = workspace;
+  const int rc = k16_launch(f24, g, part);
+  if (rc != BPK_OK) return rc;
+  const int64_t rblocks = (int64_t)(pair ? N / 2 : N) * (Cout / 8) * g.regions_x * g.regions_y;
+  BPK_REQUIRE(Cout % 8 == 0 && rblocks < (1LL << 31), "conv3x3_wino_splitk: reduce grid");
+  hipLaunchKernelGGL(wino_splitk_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0,
+                     bpk::as_stream(a.stream), workspace, S, a.bias, a.skip, a.y,
+                     reinterpret_cast<float2*>(a.stats), g);
+  BPK_LAUNCH_CHECK("conv3x3_wino_splitk_reduce");
+  return BPK_OK;
+}
+
+extern "C" int bpk_conv3x3_wino_splitk_f32(const float* x, const float* x2, int C1,
+                                           const float* pre, const float* U, const float* bias,
+                                           const float* skip, float div, float* y, float* stats,
+                                           float* workspace, int N, int Cin, int Cout, int H,
+                                           int W, void* stream) {
+  return wino_splitk(false, {x, x2, pre, U, bias, skip, y, stats, stream}, C1, div, workspace, N,
+                     Cin, Cout, H, W);
+}
+
+// bpk_conv3x3_wino_splitk_f32 with a U24 filter (bpk_conv3x3_wino_filter24_f32)
+extern "C" int bpk_conv3x3_wino_f24_splitk_f32(const float* x, const float* x2, int C1,
+                                               const float* pre, const float* U,
+                                               const float* bias, const float* skip, float div,
+                                               float* y, float* stats, float* workspace, int N,
+                                               int Cin, int Cout, int H, int W, void* stream) {
+  return wino_splitk(true, {x, x2, pre, U, bias, skip, y, stats, stream}, C1, div, workspace, N,
+                     Cin, Cout, H, W);
 }
 
 #ifdef WINO_TIMING

@@ -285,6 +285,7 @@ def filter_transform(weight, ft=False, form=16):
 
 
 GN_PART_COUNT = 128  # pixels per partial-statistics region (8 x 16)
+PRE_MAX_CIN = 1024   # input channels of a fused GroupNorm+SiLU prologue (the kernels' LDS table)
 
 
 def gn_partials(t):
@@ -1197,6 +1198,9 @@ def conv3x3(x, weight, bias=None, skip=None, div=1.0, pre=None, stats=False):
         if not (wino_supported(x, weight) or (not stats and wino_pair_supported(x, weight))):
             raise RuntimeError(f"conv3x3(pre=...): unsupported shape {tuple(x.shape)} x "
                                f"{tuple(weight.shape)}")
+        if weight.shape[1] > PRE_MAX_CIN:  # past the kernels' table: the activation, stored
+            from .norm_act import affine_silu
+            x, pre = affine_silu(x, pre), None
         return conv3x3_fwd_raw(x, weight, bias, skip, div, pre, stats)
     if stats and wino_supported(x, weight) and not _needs_grad(x, weight, bias, skip):
         return conv3x3_fwd_raw(x, weight, bias, skip, div, None, stats)
@@ -1291,10 +1295,10 @@ def gn_silu_conv3x3_ad_supported(x, weight):
     the output's GroupNorm partial statistics) or the 8-wide pair form"""
     if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32 or not _shape_ok(x, weight):
         return False
-    if weight.shape[1] > 1024:  # the prologue's GroupNorm table (kPreMaxCin)
+    if weight.shape[1] > PRE_MAX_CIN:
         return False
     return wino_supported(x, weight) or (wino_pair_supported(x, weight)
-                                         and 2 * weight.shape[1] <= 1024)
+                                         and 2 * weight.shape[1] <= PRE_MAX_CIN)
 
 
 class SkipLink:

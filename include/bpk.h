@@ -506,7 +506,9 @@ int bpk_conv3x3_wino_residual_f32(const float* x, const float* U, const float* b
                                   int Cout, int H, int W, void* stream);
 /* General form: the conv input is silu(x * s + t) with pre[n][cin] = (s, t) from
  * bpk_group_norm_affine_f32 (pre NULL: x itself), i.e. GroupNorm + SiLU + conv (+ residual
- * tail) in one launch without materialising the normalized tensor. */
+ * tail) in one launch without materialising the normalized tensor.  The kernels keep the
+ * table in LDS: pre != NULL with Cin > 1024 is an argument error here and in _ex_f32 /
+ * _splitk_f32 (apply bpk_affine_silu_f32 to x first, as op.conv.conv3x3 does). */
 int bpk_conv3x3_wino_pre_f32(const float* x, const float* pre, const float* U, const float* bias,
                              const float* skip, float div, float* y, int N, int Cin, int Cout,
                              int H, int W, void* stream);

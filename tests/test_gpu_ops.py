@@ -524,6 +524,41 @@ def test_conv3x3_winograd_prologue_8wave_form(hip, cin, cout, hw, two):
     assert (part[..., 0] - m).abs().max().item() <= 1e-5 * scale
 
 
+def test_conv3x3_prologue_over_table_limit(hip):
+    """conv3x3(pre=...) over more input channels than the kernels' GroupNorm table holds (1024):
+    Cin = 1032, the smallest multiple of 8 above it, one 8 x 16 region, with bias, residual tail
+    and statistics.  Output and the partials' mean column vs F.conv2d in float64 on
+    silu(x s + t) from the same table, 1e-5 relative to max|ref|.  The two-source form of this
+    shape is refused (the prologue of a second source needs the table in the kernel)."""
+    from op.conv import conv3x3, conv3x3_pair, gn_partials
+    cin, cout, h, w_ = 1032, 64, 8, 16
+    g = torch.Generator().manual_seed(23)
+    x = (torch.randn(1, cin, h, w_, generator=g) * 2 + 0.5).to(hip)
+    pre = torch.stack([torch.rand(1, cin, generator=g) + 0.5,
+                       torch.randn(1, cin, generator=g)], dim=-1).to(hip)
+    w = (torch.randn(cout, cin, 3, 3, generator=g) / (3 * cin ** 0.5)).to(hip)
+    b = torch.randn(cout, generator=g).to(hip)
+    skip = torch.randn(1, cout, h, w_, generator=g).to(hip)
+    div = 2.0 ** 0.5
+    p64 = pre.double()
+    a = F.silu(x.double() * p64[..., 0, None, None] + p64[..., 1, None, None])
+    ref = (skip.double() + F.conv2d(a, w.double(), b.double(), padding=1)) / div
+    with torch.no_grad():
+        out = conv3x3(x, w, b, skip=skip, div=div, pre=pre, stats=True)
+    scale = ref.abs().max().item()
+    err = (out.double() - ref).abs().max().item()
+    part, R, cnt = gn_partials(out)
+    m = out.mean((2, 3)).reshape(1, cout, 1)
+    merr = (part[..., 0] - m).abs().max().item()
+    print(f"prologue over table limit: err {err:.3e} mean err {merr:.3e} scale {scale:.3e}")
+    assert err <= 1e-5 * scale
+    assert R == 1 and cnt == 128
+    assert merr <= 1e-5 * scale
+    with torch.no_grad(), pytest.raises(RuntimeError):
+        conv3x3_pair(x[:, :512].contiguous(), x[:, 512:].contiguous(), w, b, skip=skip, div=div,
+                     pre=pre)
+
+
 # ------------------------------------------------------------------ small-channel conv3x3
 @pytest.mark.parametrize("N,cin,cout,h,w", [(2, 1, 128, 128, 128), (3, 3, 64, 20, 36),
                                              (2, 128, 1, 64, 64), (2, 256, 1, 16, 16),

@@ -1,7 +1,9 @@
 #!/bin/bash
 # Build a variant of libbpk.so with extra -D flags on one source (A/B runs; SRC=conv_winograd
 # by default):
-#   [SRC=upfirdn2d] tools/build_variant.sh NAME "-DWINO_PRIO8=1 ..."  ->  lib/variants/libbpk_NAME.so
+#   [SRC=upfirdn2d] tools/build_variant.sh NAME "-DFOO=1 ..."  ->  lib/variants/libbpk_NAME.so
+# A switch lives in the source only as long as its experiment: conv_winograd.hip has none now
+# (-DWINO_TIMING is the diagnostic build of build_wino_timing.sh).
 set -e
 cd "$(dirname "$0")/../b-pinn-kalman-filter_amd/csrc"
 make -s -j8 >/dev/null

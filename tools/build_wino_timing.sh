@@ -2,8 +2,7 @@
 # Builds the timing-instrumented Winograd library (conv_winograd.hip -DWINO_TIMING + extra
 # defines) for tools/wino_timing.py: tools/build_wino_timing.sh <name> [-DFOO=1 ...]
 # -> b-pinn-kalman-filter_amd/lib/libbpk_wino_timing<name>.so
-# The F(2x4) form (wino_timing.py --f24) is in the same library; its parent's schedule with the
-# marks is  -DWINO_F24_PRO_ORDER=0 -DWINO_F24_TAIL=0 -DWINO_F24_KEEP_TAB=0.
+# The F(2x4) form (wino_timing.py --f24) is in the same library.
 set -e
 cd "$(dirname "$0")/../b-pinn-kalman-filter_amd/csrc"
 name=$1; shift
