@@ -1642,6 +1642,155 @@ def test_fused_attention_rejects_bad_shapes(hip):
         attention(torch.zeros(1, 3, 32, 64), 1.0)
 
 
+def _attn_ref64(qkv, scale):
+    """(bmm + softmax + bmm in float64, the float64 logits)"""
+    q, k, v = qkv[:, 0].double(), qkv[:, 1].double(), qkv[:, 2].double()
+    logits = torch.bmm(q.transpose(1, 2), k) * scale
+    return torch.bmm(v, torch.softmax(logits, dim=-1).transpose(1, 2)), logits
+
+
+def _attn_splits(B, C, P):
+    """Key splits attention() takes for this shape on this device, from the workspace size
+    (S partial outputs [B, C, P] + S x [B, P] float2 statistics)."""
+    from op.attention import lib
+    n = lib.bpk_attention_workspace_bytes(B, C, P)
+    assert n % (4 * B * P * (C + 2)) == 0
+    return n // (4 * B * P * (C + 2)) if n else 1
+
+
+def _attn_unsplit(qkv, scale):
+    """bpk_attention_f32: the entry without a workspace, one workgroup per 64 queries over all
+    P keys (NKB = P / 16)."""
+    from op._lib import check, lib, stream_ptr
+    qkv = qkv.contiguous()
+    B, _, C, P = qkv.shape
+    out = torch.empty((B, C, P), dtype=torch.float32, device=qkv.device)
+    check(lib.bpk_attention_f32(qkv.data_ptr(), out.data_ptr(), B, C, P, float(scale),
+                                stream_ptr(qkv.device)), "attention")
+    return out
+
+
+def _rel(out, ref):
+    return (out.double().cpu() - ref).abs().max().item() / ref.abs().max().item()
+
+
+def test_fused_attention_nkb8_with_combine(hip):
+    """The form test_fused_attention_matches_fp32_reference never launches with a combine:
+    P = 256 in two key splits of 128 (8 key blocks per workgroup), taken when B P / 64 lies in
+    (cus / 4, cus / 2] -- B = 17 on 256 CUs.  1e-5 of max|ref| vs float64."""
+    from op.attention import attention
+    B, C, P, scale = 17, 32, 256, 0.3
+    S = _attn_splits(B, C, P)
+    assert S == 2, f"expected 2 key splits for B={B} P={P}, the device gives S={S}"
+    qkv = torch.randn(B, 3, C, P, generator=torch.Generator().manual_seed(17)) * 0.5
+    ref, _ = _attn_ref64(qkv, scale)
+    assert _rel(attention(qkv.to(hip), scale), ref) <= 1e-5
+
+
+@pytest.mark.parametrize("B,C,P,scale", [(2, 32, 128, 0.3), (3, 64, 256, 0.125)])
+def test_fused_attention_unsplit_entry_at_tiny_batches(hip, B, C, P, scale):
+    """bpk_attention_f32 at batches where attention() splits the keys: all P keys in one
+    workgroup, 8 (P = 128) and 16 (P = 256) key blocks, vs float64 and vs the split path on the
+    same input (each 1e-5 of max|ref|)."""
+    from op.attention import attention
+    S = _attn_splits(B, C, P)
+    assert S > 1, f"attention() was expected to split B={B} P={P}; S={S}"
+    qkv = torch.randn(B, 3, C, P, generator=torch.Generator().manual_seed(B + P)) * 0.5
+    ref, _ = _attn_ref64(qkv, scale)
+    one, split = _attn_unsplit(qkv.to(hip), scale), attention(qkv.to(hip), scale)
+    assert _rel(one, ref) <= 1e-5
+    assert _rel(split, ref) <= 1e-5
+    assert (one - split).abs().max().item() <= 1e-5 * ref.abs().max().item()
+
+
+@pytest.mark.parametrize("B,C,P,scale", [(2, 64, 256, 4.0), (1, 32, 128, 6.0)])
+def test_fused_attention_peaked_logits(hip, B, C, P, scale):
+    """Logits beyond float32 exp's range (max > 100: without the row-max subtraction, in the
+    kernel or in the combine's exp(m_s - M), the result is inf / NaN), split and unsplit.
+    err <= max(1e-5, 2 x the error of torch's own float32 bmm + softmax + bmm on the GPU), both
+    against float64: one-hot-like rows carry the rounding of a logit of ~150 (1e-5 of it in
+    the exponent), so 1e-5 alone is marginal for any float32 evaluation."""
+    from conftest import record_err
+    from op.attention import attention
+    S = _attn_splits(B, C, P)
+    assert S > 1, f"attention() was expected to split B={B} P={P}; S={S}"
+    qkv = torch.randn(B, 3, C, P, generator=torch.Generator().manual_seed(B * C + P))
+    ref, logits = _attn_ref64(qkv, scale)
+    assert logits.max().item() > 100 and logits.min().item() < -100
+    d = qkv.to(hip)
+    w32 = torch.softmax(torch.bmm(d[:, 0].transpose(1, 2), d[:, 1]) * scale, dim=-1)
+    e32 = _rel(torch.bmm(d[:, 2], w32.transpose(1, 2)), ref)
+    tol = max(1e-5, 2 * e32)
+    record_err(f"attention peaked B{B} C{C} P{P}: torch fp32 vs float64", e32, tol)
+    for name, out in (("split", attention(d, scale)), ("unsplit", _attn_unsplit(d, scale))):
+        assert torch.isfinite(out).all(), name
+        err = _rel(out, ref)
+        print(f"peaked {B, C, P} {name}: {err:.3e} (torch fp32 {e32:.3e})")
+        record_err(f"attention peaked B{B} C{C} P{P}: fused {name} vs float64", err, tol)
+        assert err <= tol, f"{name}: {err:.3e} > {tol:.3e} (torch fp32 {e32:.3e})"
+
+
+def _attn_both(hip, qkv, scale):
+    from op.attention import attention
+    B, _, C, P = qkv.shape
+    S = _attn_splits(B, C, P)
+    assert S > 1, f"attention() was expected to split B={B} P={P}; S={S}"
+    d = qkv.to(hip)
+    return (("split", attention(d, scale).cpu()), ("unsplit", _attn_unsplit(d, scale).cpu()))
+
+
+def test_fused_attention_uniform_rows(hip):
+    """Every key the same vector: the softmax is uniform whatever the query, and each output
+    row is the mean of v[c] (1e-6 of the largest mean)."""
+    g = torch.Generator().manual_seed(31)
+    C, P = 32, 256
+    qkv = torch.randn(1, 3, C, P, generator=g)
+    qkv[0, 1] = torch.randn(C, 1, generator=g).expand(C, P)
+    mean = qkv[0, 2].double().mean(1)
+    for name, out in _attn_both(hip, qkv, 0.5):
+        err = (out[0].double() - mean.view(C, 1)).abs().max().item() / mean.abs().max().item()
+        assert err <= 1e-6, f"{name}: {err:.3e}"
+
+
+def _dominant_qkv(key_of_query, seed, scale):
+    """qkv [1, 3, 32, 256] whose query i has logit 60 at key key_of_query[i] and |logit| < 0.5
+    elsewhere: the first len(keys) channels select, the others carry small noise."""
+    g = torch.Generator().manual_seed(seed)
+    C, P = 32, 256
+    keys = sorted(set(key_of_query))
+    qkv = torch.randn(1, 3, C, P, generator=g)
+    qkv[0, :2] *= 0.1
+    qkv[0, :2, :len(keys)] = 0.0
+    for c, j in enumerate(keys):
+        qkv[0, 1, c, j] = 60.0 / scale
+        qkv[0, 0, c, [i for i in range(P) if key_of_query[i] == j]] = 1.0
+    logits = _attn_ref64(qkv, scale)[1][0]
+    top2 = logits.topk(2, dim=1)
+    assert top2.indices[:, 0].tolist() == list(key_of_query)
+    assert (top2.values[:, 0] - top2.values[:, 1]).min().item() > 59
+    return qkv
+
+
+@pytest.mark.parametrize("pattern", ["key0", "key100", "key255", "halves", "mod4"])
+def test_fused_attention_dominant_key(hip, pattern):
+    """One key 60 above the rest per query: every output column equals that key's v column
+    (1e-5 of max|v|; the rest weighs exp(-59)).  With 4 splits of 64 keys the splits without
+    the dominant key enter the combine with exp(m_s - M) = exp(-60): a combine that drops or
+    misplaces that weight adds their unnormalised sums.  "halves" (key 3 for queries < 128, key
+    250 for the rest) and "mod4" (keys 3 / 250 / 70 / 130 by query index mod 4, i.e. different
+    within one thread's 4 outputs of the combine) pin the row statistics per query."""
+    P, scale = 256, 0.5
+    key_of_query = {"key0": [0] * P, "key100": [100] * P, "key255": [255] * P,
+                    "halves": [3] * 128 + [250] * 128,
+                    "mod4": [(3, 250, 70, 130)[i % 4] for i in range(P)]}[pattern]
+    qkv = _dominant_qkv(key_of_query, 40 + len(pattern), scale)
+    v = qkv[0, 2]
+    want = v[:, key_of_query]
+    for name, out in _attn_both(hip, qkv, scale):
+        err = (out[0] - want).abs().max().item() / v.abs().max().item()
+        assert err <= 1e-5, f"{name}: {err:.3e}"
+
+
 @pytest.mark.parametrize("mode", ["pre_stats", "pre_skip", "plain", "two_sources"])
 def test_conv3x3_winograd_large_launch(hip, mode):
     """A launch with more workgroups than CUs on the 16-cin 8-wave kernel
