@@ -478,7 +478,7 @@ class _PinnGraphStep:
       * gradients: .grad is None when the graph is captured, so autograd allocates it from
         the graph's pool and every replay rewrites it in place (no zero_grad while replaying:
         setting .grad to None would detach the parameters from the graph's buffers);
-      * native kernels only inside the graph (op.conv.native_only: no MIOpen convs, no
+      * native kernels only inside the graph (op.conv never times or picks a MIOpen conv: no
         library workspace state), the conv choices made eagerly during the warm-up.
     The observation noise is drawn eagerly into static buffers before each replay (the same
     draws, in the same order, as the eager step's two randn_like calls).
@@ -506,67 +506,66 @@ class _PinnGraphStep:
         self.noise = (torch.zeros_like(self.static[0]), torch.zeros_like(self.static[1]))
         sop = _MaskOperator(self.mask)
         params = list(model.parameters())
-        with conv_op.native_only():
-            s = torch.cuda.Stream(dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                for _ in range(2):  # kernel choices, allocator, lazy state: off the capture
-                    for p in params:
-                        p.grad = None
-                    with conv_op.batched_filters(model):
-                        loss, _pl, _dl = self.loss_fn(model, sop, self.static, self.noise)
-                        with conv_op.deferred_weight_grads(_DEFER_WGRAD):
-                            loss.backward(inputs=params)
-            # nothing of the warm-up may be freed while the capture runs: a block released
-            # mid-capture went back to the general pool and could be handed to the graph, which
-            # then shared it with eager allocations after the capture (replays read garbage a
-            # few steps later)
-            del loss, _pl, _dl
-            torch.cuda.current_stream(dev).wait_stream(s)
-            torch.cuda.synchronize(dev)
-            for p in params:
-                p.grad = None
-            for b in self.static:
-                b.grad = None
-            # the host side reads eager-owned copies the graph writes (gradients, losses); the
-            # NaN probe and the clipping norms run in a second captured graph (fewer launches)
-            gbufs = [torch.zeros_like(p) for p in params]
-            obuf = torch.zeros(4, device=dev, dtype=torch.float32)
-            g = torch.cuda.CUDAGraph()
-            # captured on the warm-up stream: the parameters' AccumulateGrad nodes (created
-            # in the warm-up) record that stream.  backward(inputs=params): the coordinate
-            # inputs' .grad (unused; the eager step accumulates them as the reference does)
-            # is neither computed nor accumulated by the replays
-            with torch.cuda.graph(g, stream=s):
-                # one recorded launch transforms every Winograd filter of the step (the job
-                # table and the transform buffers were built by the warm-up)
+        s = torch.cuda.Stream(dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            for _ in range(2):  # kernel choices, allocator, lazy state: off the capture
+                for p in params:
+                    p.grad = None
                 with conv_op.batched_filters(model):
-                    loss, pl, dl = self.loss_fn(model, sop, self.static, self.noise)
+                    loss, _pl, _dl = self.loss_fn(model, sop, self.static, self.noise)
                     with conv_op.deferred_weight_grads(_DEFER_WGRAD):
                         loss.backward(inputs=params)
-                live = [(gb, p.grad) for gb, p in zip(gbufs, params) if p.grad is not None]
-                torch._foreach_copy_([a for a, _ in live], [b for _, b in live])
-                obuf[:3].copy_(torch.stack([loss.detach(), pl.detach(), dl.detach()]))
-            # the graph's own gradient tensors stay referenced (their memory is the graph's);
-            # the parameters' .grad become the eager-owned copies from here on
-            self.graph_grads = [p.grad for p in params]
-            for p, gb in zip(params, gbufs):
-                p.grad = gb if p.grad is not None else None
-            # graph B, replayed after the (sharded: all-reduced) gradients are final: the
-            # reference's NaN probe on the pressure net's last weight, then clip_grad_norm_ of
-            # each optimizer's parameters (optimization_manager; torch's formula)
-            w = model.pressurenet.end[-1].weight
-            groups = [[p.grad for p in m.parameters() if p.grad is not None]
-                      for m in (model.flownet, model.pressurenet)]
-            gb_ = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gb_, stream=s):
-                obuf[3:].copy_(torch.isnan(w.grad).any().float().reshape(1))
-                if self.grad_clip >= 0:
-                    for grads in groups:
-                        norms = torch._foreach_norm(grads, 2.0)
-                        total = torch.linalg.vector_norm(torch.stack(norms), 2.0)
-                        coef = torch.clamp(self.grad_clip / (total + 1e-6), max=1.0)
-                        torch._foreach_mul_(grads, coef)
+        # nothing of the warm-up may be freed while the capture runs: a block released
+        # mid-capture went back to the general pool and could be handed to the graph, which
+        # then shared it with eager allocations after the capture (replays read garbage a
+        # few steps later)
+        del loss, _pl, _dl
+        torch.cuda.current_stream(dev).wait_stream(s)
+        torch.cuda.synchronize(dev)
+        for p in params:
+            p.grad = None
+        for b in self.static:
+            b.grad = None
+        # the host side reads eager-owned copies the graph writes (gradients, losses); the
+        # NaN probe and the clipping norms run in a second captured graph (fewer launches)
+        gbufs = [torch.zeros_like(p) for p in params]
+        obuf = torch.zeros(4, device=dev, dtype=torch.float32)
+        g = torch.cuda.CUDAGraph()
+        # captured on the warm-up stream: the parameters' AccumulateGrad nodes (created
+        # in the warm-up) record that stream.  backward(inputs=params): the coordinate
+        # inputs' .grad (unused; the eager step accumulates them as the reference does)
+        # is neither computed nor accumulated by the replays
+        with torch.cuda.graph(g, stream=s):
+            # one recorded launch transforms every Winograd filter of the step (the job
+            # table and the transform buffers were built by the warm-up)
+            with conv_op.batched_filters(model):
+                loss, pl, dl = self.loss_fn(model, sop, self.static, self.noise)
+                with conv_op.deferred_weight_grads(_DEFER_WGRAD):
+                    loss.backward(inputs=params)
+            live = [(gb, p.grad) for gb, p in zip(gbufs, params) if p.grad is not None]
+            torch._foreach_copy_([a for a, _ in live], [b for _, b in live])
+            obuf[:3].copy_(torch.stack([loss.detach(), pl.detach(), dl.detach()]))
+        # the graph's own gradient tensors stay referenced (their memory is the graph's);
+        # the parameters' .grad become the eager-owned copies from here on
+        self.graph_grads = [p.grad for p in params]
+        for p, gb in zip(params, gbufs):
+            p.grad = gb if p.grad is not None else None
+        # graph B, replayed after the (sharded: all-reduced) gradients are final: the
+        # reference's NaN probe on the pressure net's last weight, then clip_grad_norm_ of
+        # each optimizer's parameters (optimization_manager; torch's formula)
+        w = model.pressurenet.end[-1].weight
+        groups = [[p.grad for p in m.parameters() if p.grad is not None]
+                  for m in (model.flownet, model.pressurenet)]
+        gb_ = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gb_, stream=s):
+            obuf[3:].copy_(torch.isnan(w.grad).any().float().reshape(1))
+            if self.grad_clip >= 0:
+                for grads in groups:
+                    norms = torch._foreach_norm(grads, 2.0)
+                    total = torch.linalg.vector_norm(torch.stack(norms), 2.0)
+                    coef = torch.clamp(self.grad_clip / (total + 1e-6), max=1.0)
+                    torch._foreach_mul_(grads, coef)
         self.out = (obuf[0], obuf[1], obuf[2])
         self.obuf = obuf
         self.gbufs = [p.grad for p in params]

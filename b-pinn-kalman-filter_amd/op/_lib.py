@@ -129,9 +129,6 @@ def exported_symbols() -> list:
     return sorted(parse_header().keys())
 
 
-_PRUNE = True
-
-
 def mark_inputs(ctx, *args):
     """Record, in a custom Function's forward, which arguments are tensors: the engine keeps
     one next_functions edge per tensor argument only, so want_grad needs the mapping."""
@@ -152,7 +149,7 @@ def want_grad(ctx, i: int) -> bool:
     if not ctx.needs_input_grad[i]:
         return False
     pos = getattr(ctx, "_bpk_tpos", None)
-    if not _PRUNE or pos is None or i >= len(pos) or pos[i] is None:
+    if pos is None or i >= len(pos) or pos[i] is None:
         return True
     nf = ctx.next_functions
     if pos[i] >= len(nf):

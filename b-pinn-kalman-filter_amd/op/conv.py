@@ -6,8 +6,8 @@ its F(2x4,3x3) form with 0.75 of the MFMAs for the forward convs the 16-cin kern
 fp32 NCHW HIP tensors whose shape the kernel supports (`supported(...)`).  Backward: the
 input gradient is the same Winograd forward kernel on the flipped, transposed filter and
 the weight gradient the Winograd split-K kernel (csrc/conv_winograd_wgrad.hip) when the
-shapes qualify, else the implicit-GEMM kernels (csrc/conv_igemm.hip); MIOpen only for what no
-native kernel takes (groups, dilation, non-fp32).  The filter
+shapes qualify, else the implicit-GEMM kernels (csrc/conv_igemm.hip); aten (MIOpen) only for
+what no native kernel takes (groups, dilation, non-fp32).  The filter
 transform U = G w G^T is cached on the weight tensor itself (keyed by its version counter, which
 every in-place update such as an optimizer step bumps), so a sampler that never changes
 its weights transforms each filter once.
@@ -320,6 +320,26 @@ def ensure_gn_partials(t):
     return part, R, GN_PART_COUNT
 
 
+def _pre_arg(pre, N, C, what="conv3x3"):
+    """The GroupNorm+SiLU prologue table `pre` as the kernels read it: contiguous [N, Cin, 2]
+    (None stays None)."""
+    if pre is None:
+        return None
+    pr = pre.contiguous()
+    if tuple(pr.shape) != (N, C, 2):
+        raise RuntimeError(f"{what}: pre must be [N, Cin, 2], got {tuple(pr.shape)}")
+    return pr
+
+
+def _residual_tail(y, skip, div):
+    """(skip + y) / div as its own launch, for the kernels without the fused tail (y itself
+    when there is no skip)."""
+    if skip is None:
+        return y
+    from .norm_act import residual_rescale
+    return residual_rescale(skip.detach(), y, None, div)
+
+
 def conv3x3_fwd_raw(x, weight, bias=None, skip=None, div=1.0, pre=None, stats=False, x2=None,
                     ft=False):
     """conv(a, weight) + bias, or with `skip`: (skip + (conv + bias)) / div (one launch),
@@ -343,9 +363,7 @@ def conv3x3_fwd_raw(x, weight, bias=None, skip=None, div=1.0, pre=None, stats=Fa
     sk = None if skip is None else skip.detach().contiguous()
     if sk is not None and sk.shape != y.shape:
         raise RuntimeError(f"conv3x3: skip {tuple(sk.shape)} != output {tuple(y.shape)}")
-    pr = None if pre is None else pre.contiguous()
-    if pr is not None and tuple(pr.shape) != (N, C, 2):
-        raise RuntimeError(f"conv3x3: pre must be [N, Cin, 2], got {tuple(pr.shape)}")
+    pr = _pre_arg(pre, N, C)
     part = None
     if stats:
         R = (H // 8) * (W // 16)
@@ -370,13 +388,8 @@ def conv3x3_fwd_raw(x, weight, bias=None, skip=None, div=1.0, pre=None, stats=Fa
     return y
 
 
-_WGRAD = True  # 3x3 weight gradients on the Winograd kernel (False: MIOpen / igemm)
-
-
 def wgrad_supported(x, weight):
     """weight: the weight tensor or just its shape"""
-    if not _WGRAD:
-        return False
     if x.dtype != torch.float32 or x.dim() != 4 or not x.is_cuda:
         return False
     N, C, H, W = x.shape
@@ -401,9 +414,7 @@ def conv3x3_wgrad_raw(x, gy, wshape, bias_grad=False, pre=None):
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
     dw = torch.empty((Cout, C, 3, 3), dtype=torch.float32, device=x.device)
     db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if bias_grad else None
-    pr = None if pre is None else pre.detach().contiguous()
-    if pr is not None and tuple(pr.shape) != (N, C, 2):
-        raise RuntimeError(f"conv3x3_wgrad: pre must be [N, Cin, 2], got {tuple(pr.shape)}")
+    pr = _pre_arg(pre, N, C, "conv3x3_wgrad")
     check(lib.bpk_conv3x3_wino_wgrad_pre_f32(
         x.data_ptr(), None if pr is None else pr.data_ptr(), gy.data_ptr(), dw.data_ptr(),
         None if db is None else db.data_ptr(), ws.data_ptr(), N, C, Cout, H, W,
@@ -420,9 +431,7 @@ def conv3x3_small_raw(x, weight, bias=None, pre=None):
     w = weight.detach().contiguous()
     y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
     b = None if bias is None else bias.detach().contiguous()
-    pr = None if pre is None else pre.contiguous()
-    if pr is not None and tuple(pr.shape) != (N, C, 2):
-        raise RuntimeError(f"conv3x3: pre must be [N, Cin, 2], got {tuple(pr.shape)}")
+    pr = _pre_arg(pre, N, C)
     check(lib.bpk_conv3x3_small_f32(
         x.data_ptr(), None if pr is None else pr.data_ptr(), w.data_ptr(),
         None if b is None else b.data_ptr(), y.data_ptr(), N, C, Cout, H, W,
@@ -432,9 +441,6 @@ def conv3x3_small_raw(x, weight, bias=None, pre=None):
 
 
 # ------------------------------------------------ general convolutions on the MFMA (igemm)
-_IGEMM = True  # the implicit-GEMM kernels for the shapes below (False: MIOpen only)
-
-
 def _pair(v):
     return (v, v) if isinstance(v, int) else tuple(int(e) for e in v)
 
@@ -444,23 +450,30 @@ def igemm_supported(x, w, stride=1, padding=0, dilation=1, groups=1):
     derivatives: fp32 NCHW HIP tensors, groups = 1, dilation = 1, zero padding.  `w`: the
     weight tensor or its shape."""
     wshape = tuple(w) if isinstance(w, (tuple, list, torch.Size)) else tuple(w.shape)
-    if isinstance(w, torch.Tensor) and w.dtype != torch.float32:
-        return False
-    if not (_IGEMM and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and len(wshape) == 4 and int(groups) == 1
+    if not (x.dim() == 4 and len(wshape) == 4 and int(groups) == 1
             and _pair(dilation) == (1, 1) and wshape[1] == x.shape[1]
             and x.shape[2] + 2 * _pair(padding)[0] >= wshape[2]
             and x.shape[3] + 2 * _pair(padding)[1] >= wshape[3]):
         return False
-    return _igemm_shape_ok(tuple(x.shape), tuple(int(v) for v in wshape), _pair(stride),
-                           _pair(padding))
+    return _igemm_ok(x, w.dtype if isinstance(w, torch.Tensor) else None, tuple(x.shape),
+                     tuple(int(v) for v in wshape), _pair(stride), _pair(padding))
+
+
+def _igemm_ok(t, wdtype, xshape, wshape, s, p):
+    """The implicit-GEMM kernels take the conv of an `xshape` input with a `wshape` filter
+    (stride s, padding p: pairs; groups = 1 and dilation = 1 are the caller's to check):
+    `t`, the activation-side tensor of the call, is fp32 on the device, the weight is fp32
+    (wdtype None: only its shape is known) and the kernels' own limits hold."""
+    return (t.is_cuda and t.dtype == torch.float32 and wdtype in (None, torch.float32)
+            and _igemm_shape_ok(xshape, wshape, s, p))
 
 
 @functools.lru_cache(maxsize=4096)
 def _igemm_shape_ok(xshape, wshape, s, p):
     """The kernels' own limits (32-bit index ranges, tile counts): the workspace query of the
     forward, its adjoint and the weight gradient answers -1 for a shape they cannot run, and
-    such a conv stays on MIOpen instead of raising."""
+    such a conv stays on MIOpen instead of raising.  A padded extent below the
+    kernel's gives Ho or Wo <= 0 here, which the query rejects too."""
     N, C, H, W = xshape
     Co, _, KH, KW = wshape
     Ho, Wo = (H + 2 * p[0] - KH) // s[0] + 1, (W + 2 * p[1] - KW) // s[1] + 1
@@ -563,12 +576,13 @@ def conv2d_weight_small_cout_raw(x, wshape, gy, bias_grad=False):
 
 # Kernel selection per distinct call.  Among native kernels (Winograd vs implicit GEMM on small
 # images) the first eager call of each (op, shapes) times the candidates once and caches the
-# faster; under graph capture an unseen call takes the first candidate.  MIOpen is not a
-# candidate (round 4): every conv the networks run has a native kernel, and timing MIOpen's
-# candidates cost seconds per process (immediate mode falls back to its naive kernels for
-# several backward shapes: 0.2 s per call) for, at best, 0.3 % of a sampler step (the two
-# stride-2 FIR-down shapes at B = 64, profiles/r04_stride2_igemm_vs_miopen.txt).
-# `library_candidates()` puts MIOpen back in the igemm-vs-library choices (A/B tools).
+# faster; under graph capture an unseen call takes the first candidate.  MIOpen is never a
+# candidate: every conv the networks run has a native kernel, and timing MIOpen's candidates
+# cost seconds per process (immediate mode falls back to its naive kernels for several
+# backward shapes: 0.2 s per call) for, at best, 0.3 % of a sampler step (the two stride-2
+# FIR-down shapes at B = 64, profiles/r04_stride2_igemm_vs_miopen.txt).  It runs, through
+# aten, only what no native kernel takes (groups, dilation, non-fp32 operands, shapes past
+# the kernels' index ranges), so a step captured in a hipGraph holds no MIOpen find state.
 _CHOICE: dict = {}        # agreed choices (broadcast from rank 0 under torch.distributed)
 _CHOICE_LOCAL: dict = {}  # choices made inside local_choices(): this rank's own, never agreed
 
@@ -588,12 +602,11 @@ def _time_us(fn, reps=3):
 # Winograd kernels' per-workgroup set-up is a large share of a short launch, so 3x3 convs
 # there are timed against the implicit-GEMM kernel once per distinct call and the faster
 # kept.
-_SEL3 = True
-_SEL3_MAX_HW = 32 * 32
+_SMALL_IMG_MAX_HW = 32 * 32
 
 
 def _small_img(x):
-    return _SEL3 and _IGEMM and x.shape[2] * x.shape[3] <= _SEL3_MAX_HW
+    return x.shape[2] * x.shape[3] <= _SMALL_IMG_MAX_HW
 
 
 # Reproducibility of the per-call choice (the timing is noisy, so two runs -- or two ranks --
@@ -632,31 +645,6 @@ def _save_table():
 
 
 _LOCAL_ONLY = [False]
-_NATIVE_ONLY = [True]
-
-
-@contextlib.contextmanager
-def native_only():
-    """Inside this block the igemm-vs-MIOpen choices take the implicit-GEMM kernel (the choices
-    among native kernels stay timed) even inside `library_candidates()`: a step captured in a
-    hipGraph (the PINN step, losses.get_pinn_step_fn(graph=True)) holds only libbpk / aten
-    kernels and no MIOpen workspace or find-db state."""
-    prev, _NATIVE_ONLY[0] = _NATIVE_ONLY[0], True
-    try:
-        yield
-    finally:
-        _NATIVE_ONLY[0] = prev
-
-
-@contextlib.contextmanager
-def library_candidates():
-    """Inside this block MIOpen is timed against the implicit-GEMM kernel again (per call, the
-    faster kept): for A/B measurements only, the product default is native kernels."""
-    prev, _NATIVE_ONLY[0] = _NATIVE_ONLY[0], False
-    try:
-        yield
-    finally:
-        _NATIVE_ONLY[0] = prev
 
 
 @contextlib.contextmanager
@@ -725,59 +713,32 @@ def _pick_any(key, cands):
     return cands[0 if c is None else c]()
 
 
-def _pick(key, run_ig, run_mi):
-    """run_ig() or run_mi(), whichever the cached per-key timing says is faster (ties: igemm)."""
-    if _NATIVE_ONLY[0]:
-        return run_ig()
-    c = _decide(key, [run_ig, run_mi])
-    return run_mi() if c == 1 else run_ig()
-
-
-def conv2d_select(x, w, bias, stride, padding):
-    """F.conv2d(x, w, bias, stride, padding) (no autograd) on the faster of igemm / MIOpen."""
-    s, p = _pair(stride), _pair(padding)
-    key = ("fwd", tuple(x.shape), tuple(w.shape), s, p, bias is not None)
-    b = None if bias is None else bias.detach()
-    return _pick(key, lambda: conv2d_igemm_raw(x, w, b, s, p),
-                 lambda: F.conv2d(x.detach(), w.detach(), b, s, p))
-
-
 def conv2d_input_select(xshape, w, gy, stride, padding):
+    """torch.nn.grad.conv2d_input(xshape, w, gy, stride, padding) (no autograd) for a conv the
+    implicit-GEMM kernels take."""
     s, p = _pair(stride), _pair(padding)
     xshape = tuple(int(v) for v in xshape)
-    key = ("dgrad", xshape, tuple(w.shape), s, p)
-
-    def ig():
-        return conv2d_input_igemm_raw(xshape, w, gy, s, p)
     N, C, H, W = xshape
     if (C <= 4 and tuple(w.shape[2:]) == (3, 3) and s == (1, 1) and p == (1, 1)
             and bool(lib.bpk_conv3x3_small_supported(N, w.shape[0], C, H, W))):
         # into <= 4 channels: the conv of gy with the flipped, transposed filter on the
         # small-Cout streaming kernel (the PINN heads' input gradients), timed against igemm
-        ig_any = ig
-        ig = lambda: _pick_any(("dsc",) + key[1:], [  # noqa: E731
+        return _pick_any(("dsc", xshape, tuple(w.shape), s, p), [
             lambda: conv3x3_small_raw(gy.detach().contiguous(), _flip_t(w.detach()).contiguous()),
-            ig_any])
-    return _pick(key, ig,
-                 lambda: torch.nn.grad.conv2d_input(xshape, w.detach(), gy.detach(), s, p))
+            lambda: conv2d_input_igemm_raw(xshape, w, gy, s, p)])
+    return conv2d_input_igemm_raw(xshape, w, gy, s, p)
 
 
 def conv2d_weight_select(x, wshape, gy, stride, padding, bias_grad):
+    """(torch.nn.grad.conv2d_weight(x, wshape, gy, stride, padding), the bias gradient or
+    None) (no autograd) for a conv the implicit-GEMM kernels take."""
     s, p = _pair(stride), _pair(padding)
     wshape = tuple(int(v) for v in wshape)
-    key = ("wgrad", tuple(x.shape), wshape, s, p, bool(bias_grad))
-
-    def mi():
-        dw = torch.nn.grad.conv2d_weight(x.detach(), wshape, gy.detach(), s, p)
-        return dw, (gy.detach().sum((0, 2, 3)) if bias_grad else None)
-
-    def ig():
-        return conv2d_weight_igemm_raw(x, wshape, gy, s, p, bias_grad)
     if _small_cout_wgrad_ok(x, wshape, s, p):  # few output channels: streaming kernel vs igemm
-        ig_any = ig
-        ig = lambda: _pick_any(("wsc",) + key[1:], [  # noqa: E731
-            lambda: conv2d_weight_small_cout_raw(x, wshape, gy, bias_grad), ig_any])
-    return _pick(key, ig, mi)
+        return _pick_any(("wsc", tuple(x.shape), wshape, s, p, bool(bias_grad)), [
+            lambda: conv2d_weight_small_cout_raw(x, wshape, gy, bias_grad),
+            lambda: conv2d_weight_igemm_raw(x, wshape, gy, s, p, bias_grad)])
+    return conv2d_weight_igemm_raw(x, wshape, gy, s, p, bias_grad)
 
 
 def _flip_t(w):
@@ -788,40 +749,32 @@ def _flip_t(w):
 
 def _fwd_impl(x, w, bias=None, skip=None, div=1.0):
     """conv(x, w) + bias [-> (skip + .) / div] without autograd: Winograd MFMA kernel,
-    small-channel kernel, or MIOpen for the other shapes."""
+    small-channel kernel, implicit GEMM, or aten for the other shapes."""
     w = w.detach().contiguous()
     if wino_supported(x, w) or wino_pair_supported(x, w):
         if _small_img(x) and igemm_supported(x, w, 1, 1):
-            def ig():
-                y = conv2d_igemm_raw(x, w, None if bias is None else bias.detach(), 1, 1)
-                if skip is not None:
-                    from .norm_act import residual_rescale
-                    y = residual_rescale(skip.detach(), y, None, div)
-                return y
             key = ("f3", tuple(x.shape), tuple(w.shape), bias is not None, skip is not None)
-            return _pick_any(key, [lambda: conv3x3_fwd_raw(x.detach(), w, bias, skip, div), ig])
+            return _pick_any(key, [
+                lambda: conv3x3_fwd_raw(x.detach(), w, bias, skip, div),
+                lambda: _residual_tail(conv2d_igemm_raw(x, w, bias, 1, 1), skip, div)])
         return conv3x3_fwd_raw(x.detach(), w, bias, skip, div)
     with torch.no_grad():
         if small_supported(x, w):
             y = conv3x3_small_raw(x.detach(), w, bias)
         elif igemm_supported(x, w, 1, 1):
-            y = conv2d_select(x, w, bias, 1, 1)
+            y = conv2d_igemm_raw(x, w, bias, 1, 1)
         else:
             y = F.conv2d(x.detach(), w, None if bias is None else bias.detach(), padding=1)
-        if skip is not None:
-            from .norm_act import residual_rescale
-            y = residual_rescale(skip.detach(), y, None, div)
-    return y
+        return _residual_tail(y, skip, div)
 
 
 def _wgrad_impl(x, gy, wshape, want_b):
     """(dw, db or None) without autograd: the Winograd weight gradient (+ bias) when the
-    shape qualifies, MIOpen backward-weights otherwise."""
+    shape qualifies, else the implicit GEMM (aten for what neither takes)."""
     if wgrad_supported(x, tuple(wshape)):
         # small images, and couts past a 64-cout block (the Winograd kernel's idle waves),
         # are timed against the implicit GEMM once per distinct call
-        if ((_small_img(x) or wshape[0] % 64) and x.is_cuda and x.dtype == torch.float32
-                and igemm_supported(x, tuple(wshape), 1, 1)):
+        if (_small_img(x) or wshape[0] % 64) and igemm_supported(x, tuple(wshape), 1, 1):
             key = ("w3", tuple(x.shape), tuple(wshape))
             dw, db = _pick_any(key, [
                 lambda: conv3x3_wgrad_raw(x, gy, wshape, bias_grad=True),
@@ -842,30 +795,24 @@ def _fwd_ft_impl(x, w):
     flipped and transposed in place when the shape qualifies."""
     w = w.detach()
     N, C, H, W = x.shape
+    yshape = (N, w.shape[1], H, W)
     if (C == w.shape[0] and x.is_cuda and x.dtype == torch.float32
             and (bool(lib.bpk_conv3x3_wino_supported(N, C, w.shape[1], H, W))
                  or bool(lib.bpk_conv3x3_wino_pair_supported(N, C, w.shape[1], H, W)))):
-        if (_small_img(x) and _IGEMM and w.dtype == torch.float32
-                and _igemm_shape_ok((N, w.shape[1], H, W), tuple(w.shape), (1, 1), (1, 1))):
+        if _small_img(x) and _igemm_ok(x, w.dtype, yshape, tuple(w.shape), (1, 1), (1, 1)):
             key = ("d3", tuple(x.shape), tuple(w.shape))
             return _pick_any(key, [lambda: conv3x3_fwd_raw(x.detach(), w, ft=True),
-                                   lambda: conv2d_input_igemm_raw((N, w.shape[1], H, W), w, x, 1, 1)])
+                                   lambda: conv2d_input_igemm_raw(yshape, w, x, 1, 1)])
         return conv3x3_fwd_raw(x.detach(), w, ft=True)
-    if (_IGEMM and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32
-            and _igemm_shape_ok((N, w.shape[1], H, W), tuple(w.shape), (1, 1), (1, 1))):
+    if _igemm_ok(x, w.dtype, yshape, tuple(w.shape), (1, 1), (1, 1)):
         # conv3x3(x, flip_t(w)) is the adjoint of conv3x3(., w): the dgrad kernel, no flip
-        return conv2d_input_select((N, w.shape[1], H, W), w, x, 1, 1)
+        return conv2d_input_select(yshape, w, x, 1, 1)
     return _fwd_impl(x, _flip_t(w))
-
-
-_FT = True  # the filter transform reads the weight flipped / transposed (False: a copy)
 
 
 def _conv_ft_any(x, w):
     """conv3x3(x, _flip_t(w)) -- the backward-data conv -- recorded for autograd when grad
     mode is on, else the raw kernels."""
-    if not _FT:
-        return _conv_any(x, _flip_t(w))
     if torch.is_grad_enabled():
         return _Conv3x3FT.apply(x, w)
     return _fwd_ft_impl(x, w)
@@ -931,20 +878,19 @@ class _Conv3x3(torch.autograd.Function):
             gy = gy / ctx.div
         if want_grad(ctx, 3):
             gs = gy
-        want_b = ctx.has_bias and want_grad(ctx, 2)
+        want_w, want_b = want_grad(ctx, 1), ctx.has_bias and want_grad(ctx, 2)
         if want_grad(ctx, 0):
             gx = _conv_ft_any(gy, weight)
         if torch.is_grad_enabled():
-            if want_grad(ctx, 1):
+            if want_w:
                 gw = _Wgrad3x3.apply(x, gy, tuple(weight.shape))
             if want_b:
                 gb = gy.sum((0, 2, 3))
-        elif (want_grad(ctx, 1) and (not want_b or ctx.bias_leaf is not None)
-              and _defer_wgrad(weight, x, gy, ("3x3",), ctx.bias_leaf if want_b else None)):
-            pass  # weight (and bias) gradients deferred to the end of the backward pass
-        elif want_grad(ctx, 1) or want_b:
+        elif _deferred(weight, x, gy, ("3x3",), want_w, want_b, ctx.bias_leaf):
+            pass  # weight (and bias) gradients come at the end of the backward pass
+        elif want_w or want_b:
             dw, gb = _wgrad_impl(x, gy, tuple(weight.shape), want_b)
-            gw = dw if want_grad(ctx, 1) else None
+            gw = dw if want_w else None
         return gx, gw, gb, gs, None
 
 
@@ -1030,6 +976,15 @@ def _defer_wgrad(weight, X, GY, kind, bias=None) -> bool:
     return True
 
 
+def _deferred(weight, X, GY, kind, want_w, want_b, bias_leaf) -> bool:
+    """A conv's backward node asks: are the gradients of its `weight` (pair (X, GY)) and, with
+    want_b, of its bias left to the end of the deferred_weight_grads() block?  Only in a
+    first-order pass, for a wanted weight gradient, and when a wanted bias gradient can go
+    along (the bias is a leaf); else the node computes them now."""
+    return (not torch.is_grad_enabled() and want_w and (not want_b or bias_leaf is not None)
+            and _defer_wgrad(weight, X, GY, kind, bias_leaf if want_b else None))
+
+
 def _accum_grad(p, g):
     if p.grad is None:
         p.grad = g
@@ -1075,20 +1030,19 @@ def _two_source_ok(kind, wshape, p1, p2):
     N1, C, H, W = X1.shape
     N = N1 + X2.shape[0]
     if kind[0] == "3x3":
-        if (_WGRAD and bool(lib.bpk_conv3x3_wino_wgrad_supported(N, C, wshape[0], H, W))
+        if (bool(lib.bpk_conv3x3_wino_wgrad_supported(N, C, wshape[0], H, W))
                 and (W != 8 or N1 % 2 == 0)):
             return "wino"
-        if _IGEMM and _igemm_shape_ok((N, C, H, W), tuple(wshape), (1, 1), (1, 1)):
-            return "igemm"
-        return None
-    if kind[0] == "1x1":
-        ok = _IGEMM and _igemm_shape_ok((N, C, H, W), tuple(wshape), (1, 1), (0, 0))
-        return "igemm" if ok else None
-    cfg = kind[1]
-    if _IGEMM and int(cfg[3]) == 1 and _pair(cfg[2]) == (1, 1) and _igemm_shape_ok(
-            (N, C, H, W), tuple(wshape), _pair(cfg[0]), _pair(cfg[1])):
-        return "igemm"
-    return None
+        s, p = (1, 1), (1, 1)
+    elif kind[0] == "1x1":
+        s, p = (1, 1), (0, 0)
+    else:
+        cfg = kind[1]
+        if int(cfg[3]) != 1 or _pair(cfg[2]) != (1, 1):
+            return None
+        s, p = _pair(cfg[0]), _pair(cfg[1])
+    # (the sources are device tensors, _defer_wgrad; the weight's dtype is not looked at)
+    return "igemm" if _igemm_ok(X1, None, (N, C, H, W), tuple(wshape), s, p) else None
 
 
 def _wgrad_pairs(kind, wshape, pairs):
@@ -1190,11 +1144,7 @@ def conv3x3(x, weight, bias=None, skip=None, div=1.0, pre=None, stats=False):
     if pre is not None:
         _inference_only(x, weight, bias, skip)
         if small_supported(x, weight) and weight.shape[0] <= 4:
-            y = conv3x3_small_raw(x, weight, bias, pre)
-            if skip is not None:
-                from .norm_act import residual_rescale
-                y = residual_rescale(skip, y, None, div)
-            return y
+            return _residual_tail(conv3x3_small_raw(x, weight, bias, pre), skip, div)
         if not (wino_supported(x, weight) or (not stats and wino_pair_supported(x, weight))):
             raise RuntimeError(f"conv3x3(pre=...): unsupported shape {tuple(x.shape)} x "
                                f"{tuple(weight.shape)}")
@@ -1572,18 +1522,16 @@ class _Conv1x1(torch.autograd.Function):
             else:
                 gx = _c1_fn(gy, w2d.t())
         gw = gb = None
-        want_b = want_grad(ctx, 2)
+        want_w, want_b = want_grad(ctx, 1), want_grad(ctx, 2)
         # the parameter's gradient from this node: sum gy x^T, or for the adjoint use (w2d is
         # the parameter transposed) sum x gy^T -- the pair (X, GY) = (gy, x)
         pair = (gy, x) if ctx.wref is not None and ctx.wref.transposed else (x, gy)
-        if (not torch.is_grad_enabled() and ctx.wref is not None and want_grad(ctx, 1)
-                and (not want_b or ctx.bias_leaf is not None)
-                and _defer_wgrad(ctx.wref.t, pair[0], pair[1], ("1x1",),
-                                 ctx.bias_leaf if want_b else None)):
+        if ctx.wref is not None and _deferred(ctx.wref.t, pair[0], pair[1], ("1x1",), want_w,
+                                              want_b, ctx.bias_leaf):
             pass  # deferred to the end of the backward pass
-        elif want_grad(ctx, 1) or want_grad(ctx, 2):
-            gw, gb = _w1_fn(gy, x, bool(want_grad(ctx, 2)))
-            if not want_grad(ctx, 1):
+        elif want_w or want_b:
+            gw, gb = _w1_fn(gy, x, bool(want_b))
+            if not want_w:
                 gw = None
         return gx, gw, gb, None
 
@@ -1682,7 +1630,7 @@ class _ConvG(torch.autograd.Function):
             ctx.has_b = b is not None
             ctx.bias_leaf = b if b is not None and b.is_leaf else None
         if _ig_ok(x, w, cfg):
-            return conv2d_select(x, w, b, cfg[0], cfg[1])
+            return conv2d_igemm_raw(x, w, b, cfg[0], cfg[1])
         with torch.no_grad():
             return F.conv2d(x.detach(), w.detach(), None if b is None else b.detach(), **_cfg(cfg))
 
@@ -1691,14 +1639,12 @@ class _ConvG(torch.autograd.Function):
         x, w = ctx.saved_tensors
         gx = _convt_fn(gy, w, tuple(x.shape), ctx.cfg) if want_grad(ctx, 0) else None
         gw = gb = None
-        want_b = ctx.has_b and want_grad(ctx, 2)
-        if (not torch.is_grad_enabled() and want_grad(ctx, 1)
-                and (not want_b or ctx.bias_leaf is not None)
-                and _defer_wgrad(w, x, gy, ("gen", ctx.cfg), ctx.bias_leaf if want_b else None)):
+        want_w, want_b = want_grad(ctx, 1), ctx.has_b and want_grad(ctx, 2)
+        if _deferred(w, x, gy, ("gen", ctx.cfg), want_w, want_b, ctx.bias_leaf):
             pass  # deferred to the end of the backward pass
-        elif want_grad(ctx, 1) or want_b:
+        elif want_w or want_b:
             gw, gb = _wgrad_fn(x, gy, tuple(w.shape), ctx.cfg, bool(want_b))
-            if not want_grad(ctx, 1):
+            if not want_w:
                 gw = None
         return gx, gw, gb, None
 
@@ -1712,10 +1658,9 @@ class _ConvTG(torch.autograd.Function):
         if ctx is not None:
             ctx.save_for_backward(u, w)
             ctx.cfg = cfg
-        if (_IGEMM and u.is_cuda and u.dtype == torch.float32 and w.dtype == torch.float32
-                and int(cfg[3]) == 1 and _pair(cfg[2]) == (1, 1)
-                and _igemm_shape_ok(tuple(int(v) for v in xshape), tuple(w.shape),
-                                    _pair(cfg[0]), _pair(cfg[1]))):
+        if (int(cfg[3]) == 1 and _pair(cfg[2]) == (1, 1)
+                and _igemm_ok(u, w.dtype, tuple(int(v) for v in xshape), tuple(w.shape),
+                              _pair(cfg[0]), _pair(cfg[1]))):
             return conv2d_input_select(xshape, w, u, cfg[0], cfg[1])
         with torch.no_grad():
             return torch.nn.grad.conv2d_input(xshape, w.detach(), u.detach(), **_cfg(cfg))

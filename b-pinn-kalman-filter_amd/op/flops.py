@@ -2,7 +2,7 @@
 
 The native MFMA kernels are launched through ctypes, which torch's FlopCounterMode cannot
 see, so every launch site in op/conv.py reports its own count here while a `counting()`
-block is open; the aten ops that remain (MIOpen convolutions the per-call selection keeps,
+block is open; the aten ops that remain (the convolutions no native kernel takes,
 rocBLAS bmm of the attention blocks, linear layers) are counted inside the same block by a
 TorchDispatchMode over torch.utils.flop_counter's per-op formulas (FlopCounterMode itself
 adds module-tracking autograd hooks that cannot run inside the PINN residual's

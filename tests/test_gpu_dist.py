@@ -265,7 +265,6 @@ def _pinn_graph_worker(rank, world, port, q):
         from conftest import build_pinn_weights, load_golden, small_config
         from inverse.operators import InpaintOperator
         from models.ema import ExponentialMovingAverage
-        from op import conv as conv_op
         from pinn_kalman.pinn import PINN
         dev = torch.device("cuda:0")
         c = small_config(pinn_pde.get_config)
@@ -287,11 +286,10 @@ def _pinn_graph_worker(rank, world, port, q):
                                               optimize_fn=losses.optimization_manager(c))
             ls = []
             torch.manual_seed(11 + rank)
-            with conv_op.native_only():
-                for _ in range(4):
-                    batch = (T("f1"), T("f2"), T("x").requires_grad_(), T("y").requires_grad_(),
-                             T("t").requires_grad_(), T("target"))
-                    ls.append([float(v) for v in step_fn(state, op, batch)])
+            for _ in range(4):
+                batch = (T("f1"), T("f2"), T("x").requires_grad_(), T("y").requires_grad_(),
+                         T("t").requires_grad_(), T("target"))
+                ls.append([float(v) for v in step_fn(state, op, batch)])
             out[graph] = (ls, torch.cat([p.detach().reshape(-1) for p in m.parameters()]).cpu().numpy())
         q.put((rank, out, None))
         torch.distributed.destroy_process_group()

@@ -44,7 +44,6 @@ def test_pinn_graph_step_with_eval_steps_and_reductions_matches_eager_b64(hip, B
     from configs.pinn import pinn_pde
     from inverse.operators import InpaintOperator
     from models.ema import ExponentialMovingAverage
-    from op import conv as conv_op
     from pinn_kalman.pinn import PINN
     c = pinn_pde.get_config()
     c.device = hip
@@ -78,19 +77,18 @@ def test_pinn_graph_step_with_eval_steps_and_reductions_matches_eager_b64(hip, B
         op = InpaintOperator(mask=masks)
         tr, ev, gsum = [], [], []
         torch.manual_seed(321)
-        with conv_op.native_only():
-            for bt, be in zip(train_b, eval_b):
-                x, y, t = (v.clone().requires_grad_() for v in bt[2:5])
-                tr.append([float(v.detach()) for v in train_fn(state, op, (bt[0], bt[1], x, y, t, bt[5]))])
-                # the reference loop's eval step (pinn_lib.py:154-162) on the device between
-                # train steps, then metrics-style reductions and a launch flood
-                x, y, t = (v.clone().requires_grad_() for v in be[2:5])
-                ev.append([float(v.detach()) for v in eval_fn(state, op, (be[0], be[1], x, y, t, be[5]))])
-                gsum.append(float(sum(p.grad.double().abs().sum() for p in m.parameters()
-                                      if p.grad is not None)))
-                _flood(hip)
-                for o in opts:
-                    o.zero_grad(set_to_none=True)
+        for bt, be in zip(train_b, eval_b):
+            x, y, t = (v.clone().requires_grad_() for v in bt[2:5])
+            tr.append([float(v.detach()) for v in train_fn(state, op, (bt[0], bt[1], x, y, t, bt[5]))])
+            # the reference loop's eval step (pinn_lib.py:154-162) on the device between
+            # train steps, then metrics-style reductions and a launch flood
+            x, y, t = (v.clone().requires_grad_() for v in be[2:5])
+            ev.append([float(v.detach()) for v in eval_fn(state, op, (be[0], be[1], x, y, t, be[5]))])
+            gsum.append(float(sum(p.grad.double().abs().sum() for p in m.parameters()
+                                  if p.grad is not None)))
+            _flood(hip)
+            for o in opts:
+                o.zero_grad(set_to_none=True)
         m.train()
         return np.array(tr), np.array(ev), np.array(gsum), [p.detach().clone() for p in m.parameters()]
     tg, eg, gg, pg = run(True)

@@ -1000,17 +1000,23 @@ def test_gn_silu_conv_under_autograd_matches_unfused(hip, kind, cin, cout, hw):
         close(a, b, name)
 
 
-@pytest.mark.parametrize("k,stride,pad,cin,cout", [(3, 2, 1, 1, 16), (3, 2, 1, 16, 32), (1, 1, 0, 64, 128)])
-def test_conv2d_general_double_backward(hip, k, stride, pad, cin, cout):
-    """conv2d_general (MIOpen kernels, derivatives of every order as convolutions / conv
-    transposes / weight gradients) vs F.conv2d: forward, and second derivatives w.r.t. x, w, b
-    of a function of (dL/dx, dL/dw) (2e-5 relative)."""
+@pytest.mark.parametrize("k,stride,pad,cin,cout,dilation,groups", [
+    pytest.param(3, 2, 1, 1, 16, 1, 1, id="3-2-1-1-16"),
+    pytest.param(3, 2, 1, 16, 32, 1, 1, id="3-2-1-16-32"),
+    pytest.param(1, 1, 0, 64, 128, 1, 1, id="1-1-0-64-128"),
+    (3, 1, 2, 4, 8, 2, 1), (3, 1, 1, 4, 8, 1, 2)])
+def test_conv2d_general_double_backward(hip, k, stride, pad, cin, cout, dilation, groups):
+    """conv2d_general (derivatives of every order as convolutions / conv transposes / weight
+    gradients; the dilated and the grouped row fall through to aten at every order) vs
+    F.conv2d: forward, and second derivatives w.r.t. x, w, b of a function of (dL/dx, dL/dw)
+    (2e-5 relative)."""
     from op.conv import conv2d_general
     g = torch.Generator().manual_seed(k * 100 + stride * 10 + cin)
     x0 = torch.randn(2, cin, 16, 20, generator=g)
-    w0 = torch.randn(cout, cin, k, k, generator=g) * 0.2
+    w0 = torch.randn(cout, cin // groups, k, k, generator=g) * 0.2
     b0 = torch.randn(cout, generator=g)
-    ho, wo = (16 + 2 * pad - k) // stride + 1, (20 + 2 * pad - k) // stride + 1
+    ke = dilation * (k - 1) + 1
+    ho, wo = (16 + 2 * pad - ke) // stride + 1, (20 + 2 * pad - ke) // stride + 1
     go = torch.randn(2, cout, ho, wo, generator=g).to(hip)
     v = torch.randn(2, cin, 16, 20, generator=g).to(hip)
 
@@ -1023,8 +1029,8 @@ def test_conv2d_general_double_backward(hip, k, stride, pad, cin, cout):
         return (y.detach(),) + torch.autograd.grad(
             (gx * v).sum() + (gw * gw).sum() + (gx * gx).sum(), (x, w, b), allow_unused=True)
 
-    got = second(lambda x, w, b: conv2d_general(x, w, b, stride, pad))
-    ref = second(lambda x, w, b: F.conv2d(x, w, b, stride, pad))
+    got = second(lambda x, w, b: conv2d_general(x, w, b, stride, pad, dilation, groups))
+    ref = second(lambda x, w, b: F.conv2d(x, w, b, stride, pad, dilation, groups))
     for a, r in zip(got, ref):
         if r is None:
             assert a is None or a.abs().max().item() == 0

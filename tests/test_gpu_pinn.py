@@ -276,8 +276,8 @@ def test_pinn_step_hip_graph_replays_match_eager(hip):
     """get_pinn_step_fn(graph=True): the forward + residual derivatives + backward captured
     once and replayed for 8 steps (new batch and observation mask each step, optimizer steps
     and EMA in between) == the eager step from the same state on the configs[3] 64x64
-    network: losses at every step and the final parameters / EMA (both under
-    op.conv.native_only, so the same kernels run).  The observation noise (variance 0.01, as
+    network: losses at every step and the final parameters / EMA (both run the same native
+    kernels).  The observation noise (variance 0.01, as
     configured) comes from the same seeded generator in both runs: the graph step draws it
     into static buffers in the eager step's order."""
     import copy
@@ -286,7 +286,6 @@ def test_pinn_step_hip_graph_replays_match_eager(hip):
     from configs.pinn import pinn_pde
     from inverse.operators import InpaintOperator
     from models.ema import ExponentialMovingAverage
-    from op import conv as conv_op
     from pinn_kalman.pinn import PINN
     c = pinn_pde.get_config()
     c.device = hip
@@ -317,10 +316,9 @@ def test_pinn_step_hip_graph_replays_match_eager(hip):
         op = InpaintOperator(mask=masks)
         out = []
         torch.manual_seed(123)
-        with conv_op.native_only():
-            for bt in batches:
-                x, y, t = (v.clone().requires_grad_() for v in bt[2:5])
-                out.append([float(v.detach()) for v in step_fn(state, op, (bt[0], bt[1], x, y, t, bt[5]))])
+        for bt in batches:
+            x, y, t = (v.clone().requires_grad_() for v in bt[2:5])
+            out.append([float(v.detach()) for v in step_fn(state, op, (bt[0], bt[1], x, y, t, bt[5]))])
         if graph:
             assert step_fn.graph is not None
         return out, [p.detach().clone() for p in m.parameters()], \
