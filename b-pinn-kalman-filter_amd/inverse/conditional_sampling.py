@@ -20,6 +20,7 @@ import torch
 
 from models.utils import get_score_fn, input_grad_only
 from . import ode
+from .operators import InpaintOperator
 
 
 def _reduce_sumsq_fn(ctx):
@@ -74,6 +75,9 @@ def get_controlled_sampler(config, obsv_sde, shape, lambda_schedule, eps=1e-3, c
     which in gather form is  w * scatter(y_t) + (1 - w) * mask * x + (1 - mask) * x."""
     device = config.device
     op = obsv_sde.operator
+    if not isinstance(op, InpaintOperator):
+        raise NotImplementedError(
+            f"controlled sampler: written for the inpainting mask, not {type(op).__name__}")
 
     def drift_fn(model, x, t):
         score_fn = get_score_fn(obsv_sde.state_sde, model, train=False, continuous=True)

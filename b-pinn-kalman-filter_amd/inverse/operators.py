@@ -1,4 +1,5 @@
-"""Inpainting measurement operator in gather form (reference inverse/operators.py:8-205).
+"""Measurement operators: inpainting in gather form (reference inverse/operators.py:8-205)
+and the Gaussian blur / low-resolution operator on the HIP blur op.
 
 `InpaintOperator(mask=<iterable of masks>)`: `next()` advances to the next mask
 (cycling, reference :134-142); `op(x, keep_shape=True)` = mask * x, and
@@ -11,6 +12,10 @@ reference builds in `__init__` and which do not fit at 256^2).
 operator='inpaint_rnd' (reference datasets.py:290-300): per-pixel uniform noise
 thresholded at `ratio` (kept where u <= ratio when invert=False, Binarize
 datasets.py:41-51), one mask repeated across the batch (Repeat :54-60).
+
+`GaussianBlurOperator(std, size, factor=1)` finishes the reference's GaussianFilter
+(:77-123, declared but not instantiable): the same taps and 'symm' boundary, followed by
+keeping every `factor`-th sample; forward and transpose are single HIP launches (op.blur).
 """
 from __future__ import annotations
 
@@ -30,6 +35,11 @@ def random_mask_source(config, n=1600, generator=None):
 
 
 def get_operator(config, mask_source=None):
+    if config.inverse.operator == "gaussian_blur":
+        return GaussianBlurOperator(std=config.inverse.blur_std, size=config.inverse.blur_size)
+    if config.inverse.operator == "super_resolution":
+        return GaussianBlurOperator(std=config.inverse.blur_std, size=config.inverse.blur_size,
+                                    factor=config.inverse.factor)
     if config.inverse.operator not in ("inpaint", "inpaint_rnd"):
         raise NotImplementedError(config.inverse.operator)
     if mask_source is None:
@@ -89,3 +99,40 @@ class InpaintOperator:
         out = y.new_zeros(B, C, shape[2] * shape[3])
         out.scatter_(2, idx[:, None, :].expand(B, C, idx.shape[1]), y)
         return out.view(shape)
+
+
+class GaussianBlurOperator:
+    """y = D G x: Gaussian blur with `size` taps per axis (odd, <= 33) and half-sample
+    symmetric boundary, then every `factor`-th sample from offset (factor - 1) // 2
+    (factor = 1: deblurring; factor > 1: super-resolution).  `std` is the VARIANCE of the
+    Gaussian: the reference passes std * I as the covariance (operators.py:82), kept here.
+    Same call contract as InpaintOperator, so LOBSVSDE and the DPS sampler take either."""
+
+    def __init__(self, std=4.0, size=13, factor=1):
+        from op import blur
+        self.params = dict(std=float(std), size=int(size), factor=int(factor))
+        if self.params["factor"] < 1:
+            raise ValueError(f"blur operator: factor >= 1 required (got {factor})")
+        self.taps = blur.gaussian_taps(std, size)
+        self.factor = self.params["factor"]
+
+    def next(self):
+        """Nothing to advance: the operator is fixed."""
+
+    def out_shape(self, shape):
+        from op import blur
+        Ho, Wo = blur.out_size(shape[2], shape[3], self.taps.numel(), self.factor)
+        return (shape[0], shape[1], Ho, Wo)
+
+    def __call__(self, x, keep_shape=True, invert=False):
+        from op import blur
+        if invert:
+            raise ValueError("blur operator: no complement (invert=True is an inpainting notion)")
+        y = blur.blur2d(x, self.taps, self.factor)
+        return y if keep_shape else y.reshape(y.shape[0], y.shape[1], -1)
+
+    def transpose(self, y, shape):
+        """A^T y for y [B, C, Ho, Wo] or its flattened [B, C, Ho * Wo] form -> `shape`."""
+        from op import blur
+        y = y.reshape(self.out_shape(shape))
+        return blur.blur2d_adjoint(y, self.taps, self.factor, shape[2:])

@@ -849,6 +849,33 @@ int bpk_bayes_sample_kl_bwd_f32(const float* mu, const float* rho, const double*
                                 int64_t P, uint64_t seed, int step, const float* gW,
                                 const float* gkl, float* gmu, float* grho, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * blur2d: the blurred / low-resolution measurement operator A = D G Sym of the inverse
+ * samplers, and its adjoint, on `planes` contiguous planes.  The reference declares the
+ * operator (inverse/operators.py:76-123, GaussianFilter) without finishing it.
+ *   x [planes, H, W], K taps g (K odd, 1 <= K <= 33, p = K / 2 <= min(H, W)), stride >= 1,
+ *   o = (stride - 1) / 2 < min(H, W), Ho = ceil((H - o) / stride), Wo likewise:
+ *   (G x)[r, c] = sum_{k,l} g[k] g[l] xs[r + p - k, c + p - l], xs the half-sample symmetric
+ *                 extension of x (d c b a | a b c d | d c b a), i.e.
+ *                 scipy.signal.convolve2d(x, outer(g, g), boundary='symm', mode='same');
+ *   blur2d        : out [planes, Ho, Wo] = (G x)[stride i + o, stride j + o];
+ *   blur2d_adjoint: out [planes, H, W] = A^T y for y [planes, Ho, Wo] (H, W are the sizes
+ *                   of the input side in both calls).
+ * `taps` is a host pointer to K doubles, read during the call (the f32 entries round them
+ * to float); they travel in the kernel arguments.  One launch each; the adjoint is a
+ * gather (no atomics, bitwise reproducible).  16-byte row accesses when the planes are
+ * 16-byte aligned and the row length is a multiple of 4 (f32) / 2 (f64), scalar otherwise.
+ * Asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+int bpk_blur2d_f32(const float* x, float* out, int64_t planes, int H, int W, const double* taps,
+                   int K, int stride, void* stream);
+int bpk_blur2d_f64(const double* x, double* out, int64_t planes, int H, int W, const double* taps,
+                   int K, int stride, void* stream);
+int bpk_blur2d_adjoint_f32(const float* y, float* out, int64_t planes, int H, int W,
+                           const double* taps, int K, int stride, void* stream);
+int bpk_blur2d_adjoint_f64(const double* y, double* out, int64_t planes, int H, int W,
+                           const double* taps, int K, int stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
