@@ -1,6 +1,7 @@
 // Square-root unscented Kalman filter (Van der Merwe & Wan 2001, Merwe scaled sigma points),
 // batched over N independent filters of state dimension n <= 64 and observation dimension
-// <= 64, float32 (include/bpk.h, section "ukf").  One 256-thread block per filter:
+// <= 64, float32 (include/bpk.h, section "ukf").  One 256-thread block per filter
+// (k_innovation: one 64-thread block per filter, described at the kernel):
 //
 //   k_sigma   S staged in LDS (stride 65), 2n+1 point rows written coalesced on n.
 //   k_root    the (2n + d) x d matrix [sqrt(wi) D_1..D_2n ; R^T] lives in LDS (192 x 65 floats
@@ -439,7 +440,76 @@ __global__ __launch_bounds__(kThreads) void k_smooth(
   for (int idx = tid; idx < n * n; idx += kThreads) So[idx] = T[(idx / n) * kLd + idx % n];
 }
 
-#define UKF_GEO_CHECK(what, dimname, dim)                                                       \
+// ---------------------------------------------------------------------------------------
+// Innovation statistics of one filter per 64-thread block (one wave, lane = row), see
+// include/bpk.h.  The lower triangle of S_z is staged in one [64][65] tile (16.6 KB, so nine
+// blocks fit a CU's LDS and the 2304 filters of the shipped case are all resident at once); the
+// global read is coalesced, 16 bytes per lane when VEC4.  The substitution is gain_mean's second
+// loop, operation for operation (same divisor read, same fmaf), so e is the vector the update
+// applied, bit for bit.  The two sums are wave butterflies: a fixed order.
+constexpr int kInnovThreads = 64;
+
+template <bool VEC4>
+__global__ __launch_bounds__(kInnovThreads) void k_innovation(
+    const float* __restrict__ zmean, const float* __restrict__ Sz, const float* __restrict__ obs,
+    float* __restrict__ white, float* __restrict__ nis, float* __restrict__ loglik,
+    int* __restrict__ status, int dz) {
+  __shared__ float Zt[kMaxDim * kLd];
+  const int64_t f = blockIdx.x;
+  const int lane = threadIdx.x;
+  const float* F = Sz + f * dz * dz;
+  if (VEC4) {  // dz % 4 == 0 and a 16-byte aligned base: a quad never leaves its row
+    const int q = dz >> 2;
+    for (int idx = lane; idx < dz * q; idx += kInnovThreads) {
+      const int j = idx / q, c = (idx % q) * 4;
+      if (c <= j) {
+        const float4 t = *reinterpret_cast<const float4*>(F + j * dz + c);
+        float* z = Zt + j * kLd + c;
+        z[0] = t.x;
+        z[1] = t.y;
+        z[2] = t.z;
+        z[3] = t.w;
+      }
+    }
+  } else {
+    for (int idx = lane; idx < dz * dz; idx += kInnovThreads) {
+      const int j = idx / dz, c = idx % dz;
+      if (c <= j) Zt[j * kLd + c] = F[idx];
+    }
+  }
+  __syncthreads();
+
+  const bool in = lane < dz;
+  const float d = in ? Zt[lane * kLd + lane] : 1.f;
+  const float qnan = __int_as_float(0x7fc00000);
+  if (__any(!(d > 0.f) || !(d <= FLT_MAX))) {  // wave-uniform: no factor of a covariance
+    if (white != nullptr && in) white[f * dz + lane] = qnan;
+    if (lane == 0) {
+      nis[f] = qnan;
+      loglik[f] = qnan;
+      status[f] = 1;
+    }
+    return;
+  }
+  float v = in ? obs[f * dz + lane] - zmean[f * dz + lane] : 0.f;
+  // Zt e = v; lane c ends up holding e_c
+  for (int c = 0; c < dz; ++c) {
+    const float yc = __shfl(v, c) / Zt[c * kLd + c];
+    if (in && lane > c) v = fmaf(-yc, Zt[lane * kLd + c], v);
+    if (lane == c) v = yc;
+  }
+  if (white != nullptr && in) white[f * dz + lane] = v;
+  const float q2 = wave_sum(v * v);  // lanes >= dz hold 0
+  const float sl = wave_sum(in ? logf(d) : 0.f);
+  if (lane == 0) {
+    nis[f] = q2;
+    // the three terms are combined in double and rounded once
+    loglik[f] = (float)(-0.5 * ((double)q2 + 2.0 * (double)sl + dz * 1.8378770664093453));
+    status[f] = 0;
+  }
+}
+
+#define UKF_GEO_CHECK(what, dimname, dim)                                                      \
   BPK_REQUIRE(N >= 0 && N < (1ll << 31), "%s: N = %lld out of range", what, (long long)N);      \
   BPK_REQUIRE(n >= 1 && n <= kMaxDim, "%s: n = %d out of range [1, %d]", what, n, kMaxDim);     \
   BPK_REQUIRE(dim >= 1 && dim <= kMaxDim, "%s: %s = %d out of range [1, %d]", what, dimname,    \
@@ -529,5 +599,26 @@ extern "C" int bpk_ukf_smooth_f32(const float* mean, const float* scale_tril,
                      scale_tril, x_points, y_points, pred_mean, pred_tril, next_mean, next_tril,
                      mean_out, scale_tril_out, status, N, n, wc0, wi, groups);
   BPK_LAUNCH_CHECK("ukf_smooth");
+  return BPK_OK;
+}
+
+extern "C" int bpk_ukf_innovation_f32(const float* z_mean, const float* z_tril, const float* obs,
+                                      float* white, float* nis, float* loglik, int* status,
+                                      int64_t N, int dz, void* stream) {
+  BPK_REQUIRE(N >= 0 && N < (1ll << 31), "ukf_innovation: N = %lld out of range", (long long)N);
+  BPK_REQUIRE(dz >= 1 && dz <= kMaxDim, "ukf_innovation: dz = %d out of range [1, %d]", dz,
+              kMaxDim);
+  UKF_PTR("ukf_innovation", z_mean);
+  UKF_PTR("ukf_innovation", z_tril);
+  UKF_PTR("ukf_innovation", obs);
+  UKF_PTR("ukf_innovation", nis);
+  UKF_PTR("ukf_innovation", loglik);
+  UKF_PTR("ukf_innovation", status);
+  if (N == 0) return BPK_OK;
+  const bool vec4 = dz % 4 == 0 && reinterpret_cast<uintptr_t>(z_tril) % 16 == 0;
+  hipLaunchKernelGGL(vec4 ? k_innovation<true> : k_innovation<false>, dim3((unsigned)N),
+                     dim3(kInnovThreads), 0, bpk::as_stream(stream), z_mean, z_tril, obs, white,
+                     nis, loglik, status, dz);
+  BPK_LAUNCH_CHECK("ukf_innovation");
   return BPK_OK;
 }

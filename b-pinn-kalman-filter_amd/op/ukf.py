@@ -22,6 +22,15 @@ scramble patches across fields.
 Factors are lower triangular; only the lower triangle of a noise factor is read.  `status`
 (int32 [N]) is 1 where a rank-1 downdate lost positive definiteness (that filter's outputs are
 finite but otherwise unspecified; the others are unaffected), else 0.
+
+Consistency.  `innovation` reports what an update's innovation says about the filter: the
+whitened innovation e = S_z^-1 (z - zhat) (the very vector `kalman_update` applies), the
+normalized innovation squared nis = e^T e (chi-square with dz degrees of freedom when the
+filter's covariances are right) and the innovation log-likelihood
+-0.5 (nis + 2 sum_i log S_z[i,i] + dz log(2 pi)) = log N(z; zhat, S_z S_z^T).  Its `status` is 1
+where z_tril's diagonal is not positive and finite; that filter's statistics are NaN.  The
+reference has no counterpart (torchfilter reports none); the truth is the closed-form Gaussian
+evidence in float64.
 """
 from __future__ import annotations
 
@@ -184,3 +193,28 @@ def rts_smooth(mean, scale_tril, x_points, y_points, pred_mean, pred_tril, next_
                                  s1.data_ptr(), status.data_ptr(), N, n, float(wc0), float(wi),
                                  int(groups), stream_ptr(mean.device)), what)
     return m1, s1, status
+
+
+def innovation(z_mean, z_tril, obs, white=True):
+    """(z_mean [N, dz], z_tril [N, dz, dz]) from `unscented_root` of the measured points and
+    obs [N, dz] -> (white [N, dz], nis [N], loglik [N], status int32 [N]); `white=False` skips
+    the whitened innovation (None is returned in its place)."""
+    what = "ukf.innovation"
+    _f32(what, z_mean, z_tril, obs)
+    if z_mean.ndim != 2:
+        raise RuntimeError(f"{what}: z_mean must be [N, dz]")
+    N, dz = z_mean.shape
+    _shape(what, "z_tril", z_tril, (N, dz, dz))
+    _shape(what, "obs", obs, (N, dz))
+    _geo(what, N, 1, 1, dz=dz)
+    z_mean, z_tril, obs = z_mean.contiguous(), z_tril.contiguous(), obs.contiguous()
+    dev = z_mean.device
+    e = torch.empty(N, dz, device=dev, dtype=torch.float32) if white else None
+    nis = torch.empty(N, device=dev, dtype=torch.float32)
+    loglik = torch.empty(N, device=dev, dtype=torch.float32)
+    status = torch.empty(N, device=dev, dtype=torch.int32)
+    check(lib.bpk_ukf_innovation_f32(z_mean.data_ptr(), z_tril.data_ptr(), obs.data_ptr(),
+                                     None if e is None else e.data_ptr(), nis.data_ptr(),
+                                     loglik.data_ptr(), status.data_ptr(), N, dz,
+                                     stream_ptr(dev)), what)
+    return e, nis, loglik, status

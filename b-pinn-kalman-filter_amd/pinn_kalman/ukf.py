@@ -31,6 +31,20 @@ uses the frames after t.  `UKF.filter` / `UKF.smooth` are the same on fields, an
 `PINN_KF` (reference :46-82) couples the filter to a `B_PINN`: each step the Monte-Carlo mean
 of the predicted flow and pressure is the pseudo-observation of (u, v, p) and their standard
 deviation the observation's uncertainty (`IdentityKFMeasure.update_uncertainty`).
+
+Consistency (`diagnostics=True`, `gate=...`, `valid=...`; all off by default, and then every
+launch and result is what it was without them).  An update then also calls
+`op.ukf.innovation` on the (z_mean, z_tril) it already has and keeps, per filter, the
+normalized innovation squared `nis` = e^T e with e = S_z^-1 (z - zhat) and the innovation
+log-likelihood `loglik` = log N(z; zhat, S_z S_z^T).  A consistent filter has nis ~ chi-square
+with dz degrees of freedom (mean dz), and the logliks of a sequence add up to the evidence of
+the noise choices (initial variance, process noise, observation factor) -- the number to
+compare when tuning them.  `gate` (a float, e.g. a chi-square quantile for dz degrees of
+freedom; the caller computes it, no scipy here) keeps filters with nis > gate (or NaN) out of
+the update; `valid` (bool [N]) marks filters that have no observation at this step.  Both
+leave the rejected filters' predicted belief untouched, bit for bit, by a `torch.where` over
+the outputs of the one update kernel.  Nothing is read on the host: `valid`, `accepted` and
+the statistics stay on the device.
 """
 from __future__ import annotations
 
@@ -47,12 +61,16 @@ class FilterHistory:
     """What `SquareRootUKF.filter` keeps of T steps, on the device: `means` [T+1, N, n] and
     `scale_trils` [T+1, N, n, n] (index 0: the belief before the first step, index t + 1: the
     posterior of step t), `pred_means` [T, N, n] and `pred_trils` [T, N, n, n] (the prediction
-    of step t) and `controls` (a list of length T)."""
+    of step t) and `controls` (a list of length T).  When the filter kept innovation statistics
+    (diagnostics, a gate or a `valid` argument): `nis`, `logliks` [T, N] (NaN where a filter had
+    no observation) and `accepted` (bool [T, N]: the update was applied); else None."""
 
-    def __init__(self, means, scale_trils, pred_means, pred_trils, controls):
+    def __init__(self, means, scale_trils, pred_means, pred_trils, controls, *, nis=None,
+                 logliks=None, accepted=None):
         self.means, self.scale_trils = means, scale_trils
         self.pred_means, self.pred_trils = pred_means, pred_trils
         self.controls = controls
+        self.nis, self.logliks, self.accepted = nis, logliks, accepted
 
     def __len__(self):
         return self.pred_means.shape[0]
@@ -64,14 +82,24 @@ class SquareRootUKF(nn.Module):
     Attributes after `initialize_beliefs`: `belief_mean` [N, n], `belief_scale_tril`
     [N, n, n] (lower triangular, P = S S^T) and `status` (int32 [N] on the device, OR-ed over
     every kernel since initialisation, never read on the host: 1 where a Cholesky downdate lost
-    positive definiteness, see `op.ukf`)."""
+    positive definiteness, see `op.ukf`).
 
-    def __init__(self, dynamics, measurement, alpha=1., beta=0., kappa=0., groups=1):
+    `diagnostics=True`: every update also stores `nis`, `loglik` (float32 [N]) and `accepted`
+    (bool [N]) of that step (module docstring).  `gate`: the NIS threshold above which a
+    filter's update is rejected; implies the statistics.  With neither (and no `valid`
+    argument) the three stay None and the filter runs exactly the launches it ran without
+    them."""
+
+    def __init__(self, dynamics, measurement, alpha=1., beta=0., kappa=0., groups=1,
+                 diagnostics=False, gate=None):
         super().__init__()
         self.dynamics_model = dynamics
         self.measurement_model = measurement
         self.alpha, self.beta, self.kappa = float(alpha), float(beta), float(kappa)
         self.groups = int(groups)
+        self.diagnostics = bool(diagnostics)
+        self.gate = None if gate is None else float(gate)
+        self.nis = self.loglik = self.accepted = None
         self.belief_mean = self.belief_scale_tril = self.status = None
         self._filtered = False
 
@@ -113,7 +141,14 @@ class SquareRootUKF(nn.Module):
             y, self._noise(q), n, wm0, wc0, wi, self.groups)
         self.status |= st
 
-    def update(self, observations):
+    def update(self, observations, valid=None, statistics=False):
+        """Measurement update.  `valid` (bool [N] on the device, False = this filter has no
+        observation at this step) and the gate decide which filters are *accepted*: valid and
+        nis <= gate (a NaN nis compares False and is rejected).  Accepted filters get exactly
+        what `kalman_update` returns, rejected ones keep the predicted belief bit for bit (and
+        the update's status is not held against them); `nis` / `loglik` are NaN where `valid`
+        is False.  `statistics=True` asks for the statistics of this call alone (`filter` does,
+        for the observed steps of a sequence with gaps)."""
         n = self.belief_mean.shape[1]
         _, wm0, wc0, wi = self.weights
         x = self._points()
@@ -123,46 +158,133 @@ class SquareRootUKF(nn.Module):
             z, r = self.measurement_model(x)
         z_mean, z_tril, st = K.unscented_root(z, self._noise(r), n, wm0, wc0, wi, self.groups)
         self.status |= st
-        self.belief_mean, self.belief_scale_tril, st = K.kalman_update(
+        mean, tril, st = K.kalman_update(
             self.belief_mean, self.belief_scale_tril, x, z, z_mean, z_tril, observations, wc0, wi,
             self.groups)
+        if statistics or self.diagnostics or self.gate is not None or valid is not None:
+            _, nis, loglik, ist = K.innovation(z_mean, z_tril, observations, white=False)
+            self.status |= ist
+            accepted = None
+            if valid is not None:
+                if valid.dtype != torch.bool or tuple(valid.shape) != nis.shape:
+                    raise ValueError(f"SquareRootUKF.update: valid must be bool "
+                                     f"[{nis.shape[0]}], got {valid.dtype} {list(valid.shape)}")
+                accepted = valid = valid.to(nis.device)
+                nan = torch.full_like(nis, float("nan"))
+                nis, loglik = torch.where(valid, nis, nan), torch.where(valid, loglik, nan)
+            if self.gate is not None:
+                inside = nis <= self.gate
+                accepted = inside if accepted is None else accepted & inside
+            if accepted is None:
+                accepted = torch.ones_like(nis, dtype=torch.bool)
+            else:
+                mean = torch.where(accepted.unsqueeze(1), mean, self.belief_mean)
+                tril = torch.where(accepted.view(-1, 1, 1), tril, self.belief_scale_tril)
+                st = torch.where(accepted, st, torch.zeros_like(st))
+            self.nis, self.loglik, self.accepted = nis, loglik, accepted
+        self.belief_mean, self.belief_scale_tril = mean, tril
         self.status |= st
 
+    def _skip(self):
+        """A step without an observation: the prediction stands, the statistics are NaN."""
+        N, dev = self.belief_mean.shape[0], self.belief_mean.device
+        self.nis = torch.full((N,), float("nan"), device=dev)
+        self.loglik = self.nis.clone()
+        self.accepted = torch.zeros(N, device=dev, dtype=torch.bool)
+
+    def _measure(self, observations, valid, statistics=False):
+        """The second half of a step: `valid` is None / True (update), False (a missing frame)
+        or a bool [N] device mask."""
+        if valid is None or valid is True:
+            self.update(observations, statistics=statistics)
+        elif valid is False:
+            self._skip()
+        else:
+            self.update(observations, valid)
+
     @torch.no_grad()
-    def forward(self, observations, controls=None):
-        """One filter step; returns the posterior mean [N, n]."""
+    def forward(self, observations, controls=None, valid=None):
+        """One filter step; returns the posterior mean [N, n].  `valid`: None (every filter
+        observes), bool [N] on the device (see `update`), or a Python False (a missing frame:
+        predict only, the measurement model is not called)."""
         if self.belief_mean is None:
             raise RuntimeError("SquareRootUKF: call initialize_beliefs first")
         self.predict(controls)
-        self.update(observations)
+        self._measure(observations, valid)
         return self.belief_mean
 
     @torch.no_grad()
-    def filter(self, observations, controls=None):
+    def filter(self, observations, controls=None, valid=None):
         """T `forward` steps from the current belief over `observations` ([T, N, dz] or a
         sequence of T tensors [N, dz]) and `controls` (None or a sequence of length T);
-        bit-identical to T calls of `forward`.  Returns the `FilterHistory` `smooth` needs."""
+        bit-identical to T calls of `forward`.  Returns the `FilterHistory` `smooth` needs.
+
+        `valid`: None, or T entries, one per step -- a sequence (or a host tensor [T]) of
+        Python bools / None / bool [N] device tensors, or a device tensor [T] or [T, N].  A
+        step whose entry is a Python False or None is a missing frame: predict only, neither
+        the measurement model nor the update runs (its observation is not looked at and may be
+        None), and its statistics are NaN.  Entries on the device are never read on the host:
+        they go to `update` as masks."""
         if self.belief_mean is None:
             raise RuntimeError("SquareRootUKF: call initialize_beliefs first")
         T = len(observations)
         controls = [None] * T if controls is None else list(controls)
         if len(controls) != T:
             raise ValueError(f"SquareRootUKF.filter: {len(controls)} controls for {T} observations")
+        N, n = self.belief_mean.shape
+        dev = self.belief_mean.device
+        steps = self._valid_steps(valid, T, N)
+        keep = self.diagnostics or self.gate is not None or valid is not None
         means, trils, pmeans, ptrils = [self.belief_mean], [self.belief_scale_tril], [], []
+        nis, logliks, accepted = [], [], []
         for t in range(T):
             self.predict(controls[t])
             pmeans.append(self.belief_mean)
             ptrils.append(self.belief_scale_tril)
-            self.update(observations[t])
+            self._measure(None if steps[t] is False else observations[t], steps[t], keep)
             means.append(self.belief_mean)
             trils.append(self.belief_scale_tril)
-        N, n = self.belief_mean.shape
-        dev = self.belief_mean.device
+            if keep:
+                nis.append(self.nis)
+                logliks.append(self.loglik)
+                accepted.append(self.accepted)
         self._filtered = True
+        stats = {}
+        if keep:
+            stats = dict(
+                nis=torch.stack(nis) if T else torch.empty(0, N, device=dev),
+                logliks=torch.stack(logliks) if T else torch.empty(0, N, device=dev),
+                accepted=torch.stack(accepted) if T else torch.empty(0, N, device=dev,
+                                                                     dtype=torch.bool))
         return FilterHistory(torch.stack(means), torch.stack(trils),
                              torch.stack(pmeans) if T else torch.empty(0, N, n, device=dev),
                              torch.stack(ptrils) if T else torch.empty(0, N, n, n, device=dev),
-                             controls)
+                             controls, **stats)
+
+    @staticmethod
+    def _valid_steps(valid, T, N):
+        """`filter`'s `valid` -> T entries, each True (plain update), False (skip) or a bool
+        [N] device mask."""
+        if valid is None:
+            return [True] * T
+        if torch.is_tensor(valid):
+            if valid.dtype != torch.bool or valid.ndim not in (1, 2) or valid.shape[0] != T:
+                raise ValueError(f"SquareRootUKF.filter: valid must be bool [{T}] or "
+                                 f"[{T}, {N}], got {valid.dtype} {list(valid.shape)}")
+            if valid.ndim == 1 and not valid.is_cuda:
+                valid = valid.tolist()
+            elif valid.ndim == 1:  # on the device: never read, becomes a mask per step
+                valid = valid.unsqueeze(1).expand(T, N)
+        steps = []
+        if len(valid) != T:
+            raise ValueError(f"SquareRootUKF.filter: {len(valid)} valid entries for {T} "
+                             "observations")
+        for v in valid:
+            if torch.is_tensor(v):
+                steps.append(v if v.ndim else v.expand(N))
+            else:
+                steps.append(v is not None and bool(v))
+        return steps
 
     @torch.no_grad()
     def smooth(self, history):
@@ -175,7 +297,13 @@ class SquareRootUKF(nn.Module):
         keeps a step's history at 2 (N n^2 + N n) floats (76 MB at 2304 filters of n = 64,
         against 228 MB with both point sets), and requires a deterministic dynamics model:
         the second call must return the points the prediction was made from.  `NSDynamics`
-        is one.  Statuses are OR-ed into `self.status`."""
+        is one.  Statuses are OR-ed into `self.status`.
+
+        A gated, invalid or skipped step needs nothing special: its posterior is its
+        prediction, so its entry of `history.means` equals that of `history.pred_means`, and
+        the backward recursion treats it like any other step (the step carried no
+        information; the smoothed belief there comes from the dynamics and the later
+        frames)."""
         if self.belief_mean is None or not self._filtered:
             raise RuntimeError("SquareRootUKF: call filter before smooth")
         if not isinstance(history, FilterHistory):
@@ -219,9 +347,19 @@ class UKF(nn.Module):
     deviation and zero innovation and is left to the dynamics.
 
     `filter(obsv_seq)` / `smooth(obsv_seq)` process a recorded sequence [T, B, 4, H, W];
-    `smooth` needs a deterministic dynamics model (see `SquareRootUKF.smooth`)."""
+    `smooth` needs a deterministic dynamics model (see `SquareRootUKF.smooth`).
 
-    def __init__(self, config, compat=True, mask=None):
+    `diagnostics` / `gate` are `SquareRootUKF`'s.  `valid` (`forward`: bool [B]; `filter`:
+    [T] or [T, B]) marks whole frames of a sample as present; it is expanded to the filter rows
+    in `patch`'s (channel, sample, patch) order.  After `filter`, `nis_maps()` and
+    `log_likelihood()` read the statistics of `self.history`.  Under `mask`, an unobserved
+    density pixel has zero deviation and zero innovation, and S_z is block diagonal there with
+    the measurement model's own factor entry r on the diagonal (`IdentityKFMeasure` hands the
+    filter `config.inverse.variance` as that factor entry, so the pixel's innovation variance
+    is r^2): the pixel adds zero to the NIS and the constant -0.5 log(2 pi r^2) to the
+    log-likelihood."""
+
+    def __init__(self, config, compat=True, mask=None, diagnostics=False, gate=None):
         super().__init__()
         self.dim = config.kf.patch_size
         self.size = config.data.image_size
@@ -234,7 +372,8 @@ class UKF(nn.Module):
             self.measurement = InpaintKFMeasure(config, mask)
             self.mask = self.measurement.mask_field.to(self.device)
         self.ukf = SquareRootUKF(self.dynamic, self.measurement, alpha=1.0, beta=0.0, kappa=0.0,
-                                 groups=4)
+                                 groups=4, diagnostics=diagnostics, gate=gate)
+        self.history = None
 
     def initialize(self, x0=None, var=0.01):
         d = self.dim ** 2
@@ -248,10 +387,26 @@ class UKF(nn.Module):
         tril = (torch.eye(d, device=self.device) * float(var) ** 0.5).unsqueeze(0).expand(N, -1, -1)
         self.ukf.initialize_beliefs(mean=mean, scale_tril=tril)
 
-    def forward(self, obsv):
-        """obsv [B, 4, H, W] -> filtered fields [B, 4, H, W]."""
-        pred = self.ukf(self._observation(obsv))
+    def forward(self, obsv, valid=None):
+        """obsv [B, 4, H, W] -> filtered fields [B, 4, H, W].  `valid`: None, bool [B] on the
+        device (samples whose frame is present) or a Python False (no frame: predict only)."""
+        if valid is None:
+            pred = self.ukf(self._observation(obsv))
+        elif valid is False:
+            pred = self.ukf(None, valid=False)
+        else:
+            pred = self.ukf(self._observation(obsv), valid=self._valid_rows(valid))
         return unpatch(pred, self.dim, self.size, 4)
+
+    def _valid_rows(self, valid):
+        """bool [..., B] (frames of a sample) -> bool [..., N]: filter rows are (channel,
+        sample, patch)."""
+        if not torch.is_tensor(valid) or valid.dtype != torch.bool or valid.ndim < 1:
+            raise ValueError("UKF: valid must be a bool tensor over the samples")
+        patches = (self.size // self.dim) ** 2
+        lead, B = valid.shape[:-1], valid.shape[-1]
+        v = valid.reshape(*lead, 1, B, 1).expand(*lead, 4, B, patches)
+        return v.reshape(*lead, 4 * B * patches)
 
     def _observation(self, obsv):
         """[B, 4, H, W] -> the filters' observation rows (density masked under `mask`)."""
@@ -263,15 +418,39 @@ class UKF(nn.Module):
         """[T, N, n] -> [T, B, 4, H, W]."""
         return torch.stack([unpatch(m, self.dim, self.size, 4) for m in means])
 
-    def filter(self, obsv_seq):
-        """obsv_seq [T, B, 4, H, W] -> filtered fields [T, B, 4, H, W]: T `forward` steps."""
-        self.history = self.ukf.filter([self._observation(o) for o in obsv_seq])
+    def filter(self, obsv_seq, valid=None):
+        """obsv_seq [T, B, 4, H, W] -> filtered fields [T, B, 4, H, W]: T `forward` steps.
+        `valid`: None, [T] (whole steps; host bools make a False step predict-only, see
+        `SquareRootUKF.filter`) or a bool tensor [T, B] (frames of single samples)."""
+        if torch.is_tensor(valid) and valid.ndim == 2:
+            valid = self._valid_rows(valid)
+        self.history = self.ukf.filter([self._observation(o) for o in obsv_seq], valid=valid)
         return self._fields(self.history.means[1:])
 
-    def smooth(self, obsv_seq):
+    def _statistic(self, name):
+        h = self.history
+        if h is None or getattr(h, name) is None:
+            raise RuntimeError("UKF: no innovation statistics: build the filter with "
+                               "diagnostics=True (or a gate / valid) and call filter() first")
+        v = getattr(h, name)
+        num = self.size // self.dim
+        return v.reshape(v.shape[0], 4, -1, num, num).transpose(1, 2)  # [T, B, 4, H/p, W/p]
+
+    def nis_maps(self):
+        """[T, B, 4, H/p, W/p]: the NIS of every (channel, patch) filter at every step of the
+        last `filter` (NaN where a frame was missing); a consistent filter has mean p^2."""
+        return self._statistic("nis")
+
+    def log_likelihood(self):
+        """[T, B]: the innovation log-likelihood of every frame of the last `filter`, summed
+        over channels and patches (the filters are independent, so their evidences add); NaN
+        where the frame was missing."""
+        return self._statistic("logliks").sum(dim=(2, 3, 4))
+
+    def smooth(self, obsv_seq, valid=None):
         """obsv_seq [T, B, 4, H, W] -> (filtered, smoothed), both [T, B, 4, H, W]: `filter`,
         then the backward pass; smoothed[T-1] is filtered[T-1]."""
-        filtered = self.filter(obsv_seq)
+        filtered = self.filter(obsv_seq, valid=valid)
         means_s, _ = self.ukf.smooth(self.history)
         return filtered, self._fields(means_s[1:])
 
@@ -288,13 +467,16 @@ class PINN_KF(nn.Module):
     (previous frame, f); mean and unbiased std of the full-size flow and of the pressure; the
     stds go to `measurement.update_uncertainty`; the observation cat[f, flow mean, pressure
     mean] goes through one `UKF.forward`.  Returns the filtered fields [B, 4, H, W].
-    `mask` / `compat` are the UKF's."""
+    `mask` / `compat` / `diagnostics` / `gate` are the UKF's: with diagnostics on,
+    `self.ukf.ukf.nis`, `.loglik` and `.accepted` describe the step `forward` just made (how
+    well the B-PINN's Monte-Carlo std explains its own pseudo-observation)."""
 
-    def __init__(self, config, compat=True, mask=None):
+    def __init__(self, config, compat=True, mask=None, diagnostics=False, gate=None):
         super().__init__()
         self.device = config.device
         self.patch_size = config.kf.patch_size
-        self.ukf = UKF(config, compat=compat, mask=mask).to(self.device)
+        self.ukf = UKF(config, compat=compat, mask=mask, diagnostics=diagnostics,
+                       gate=gate).to(self.device)
         self.pinn = B_PINN(config).to(self.device)
         self.f_prev = None
 

@@ -802,8 +802,28 @@ int bpk_instance_norm_act_bwd2_f64(const double* v, const double* dy, const doub
  * status [N] int32 is written 0, or 1 where a downdate met S_kk^2 - x_k^2 <= 0: that
  * diagonal becomes eps_f32 |S_kk|, the rest of that vector is dropped, the filter's
  * outputs are finite but otherwise unspecified, and other filters are unaffected.
+ *   innovation: the statistics of the innovation of an update, from the (z_mean [N, dz],
+ *           z_tril [N, dz, dz]) `root` returned for the measured points and obs [N, dz]; it has
+ *           no counterpart in the reference (torchfilter reports none), the truth is the
+ *           Gaussian evidence in closed form.  Only the lower triangle of z_tril is read.
+ *             white [N, dz] = e = S_z^-1 (obs - z_mean), by forward substitution in the order
+ *                             of the update's own solve: e is the vector the update applied,
+ *                             bit for bit.  `white` may be NULL.
+ *             nis [N]       = e^T e, the normalized innovation squared
+ *                             (= (z - zhat)^T (S_z S_z^T)^-1 (z - zhat)).
+ *             loglik [N]    = log N(obs; z_mean, S_z S_z^T)
+ *                           = -0.5 (nis + 2 sum_i log S_z[i,i] + dz log(2 pi)); logf per
+ *                             diagonal entry, the three terms combined in double, rounded once.
+ *             status [N]    = 1 where a diagonal entry of z_tril is not > 0 or not finite:
+ *                             white, nis and loglik of that filter are NaN and the other
+ *                             filters are unaffected; else 0.  (A NaN elsewhere in the inputs
+ *                             propagates into that filter's outputs with status 0.)
+ *           Both sums are reduced in a fixed order.
  * No scratch, no atomics (bit-reproducible), asynchronous on `stream`.
  * ------------------------------------------------------------------------- */
+int bpk_ukf_innovation_f32(const float* z_mean, const float* z_tril, const float* obs,
+                           float* white, float* nis, float* loglik, int* status, int64_t N,
+                           int dz, void* stream);
 int bpk_ukf_sigma_points_f32(const float* mean, const float* scale_tril, float* points, int64_t N,
                              int n, float gamma, int groups, void* stream);
 int bpk_ukf_root_f32(const float* points, const float* noise_tril, float* mean, float* scale_tril,
