@@ -2,7 +2,11 @@
 
 Reference API: op/ns_step.py:19-26 -> ns_step_forward.update_{density,velocity,
 pressure}(tensor, tensor, float dt, float dx) (op/ns_step.cpp:45-102); forward
-only, no autograd, out-of-place.
+only and out-of-place there.  Here `update_density`, `update_pressure`,
+`update_velocity(compat=False)` and `full_step(compat=False)` are also differentiable to
+first order (HIP gather adjoints, csrc/ns_step_vjp.hip) when grad mode is on and an input
+requires grad; without that they run exactly the forward launches.  A double backward
+raises.  `compat=True` stays forward-only and builds no graph.
 
 `compat=True` (default, = reference behaviour) reproduces the unbind-stride quirk
 of update_velocity (op/ns_step.cpp:70): for batch >= 2 the u / v views of the
@@ -16,9 +20,11 @@ Lifted: the reference maps the batch to threadIdx.x (B <= 1024); any B works her
 """
 from __future__ import annotations
 
+import functools
+
 import torch
 
-from ._lib import check, lib, require_hip, stream_ptr
+from ._lib import check, lib, ptr, require_hip, stream_ptr
 
 
 def _check(name, *ts):
@@ -40,9 +46,29 @@ def _workspace(op, B, nx, ny, device):
     return torch.empty(max(nbytes // 4, 1), device=device, dtype=torch.float32)
 
 
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in ts)
+
+
+def _vjp_workspace(op, B, nx, ny, device):
+    nbytes = lib.bpk_ns_vjp_workspace_bytes(op, B, nx, ny)
+    return torch.empty(max(nbytes // 4, 1), device=device, dtype=torch.float32)
+
+
+def _cot(g):
+    """Cotangent for the ABI: None stays None (NULL), anything else contiguous."""
+    return None if g is None else g.contiguous()
+
+
 def update_density(dens, vel, dt, dx):
     _check("update_density", dens, vel)
     dens, vel = dens.contiguous(), vel.contiguous()
+    if _wants_grad(dens, vel):
+        return _UpdateDensity.apply(dens, vel, float(dt), float(dx))
+    return _update_density(dens, vel, dt, dx)
+
+
+def _update_density(dens, vel, dt, dx):
     B, nx, ny = _geo(dens)
     out = torch.empty_like(dens)
     ws = _workspace(0, B, nx, ny, dens.device)
@@ -53,8 +79,16 @@ def update_density(dens, vel, dt, dx):
 
 
 def update_velocity(vel, pres, dt, dx, compat=True):
+    """compat=False is differentiable (first order); compat=True is the reference's
+    forward-only op and builds no autograd graph."""
     _check("update_velocity", vel, pres)
     vel, pres = vel.contiguous(), pres.contiguous()
+    if not compat and _wants_grad(vel, pres):
+        return _UpdateVelocity.apply(vel, pres, float(dt), float(dx))
+    return _update_velocity(vel, pres, dt, dx, compat)
+
+
+def _update_velocity(vel, pres, dt, dx, compat):
     B, nx, ny = _geo(vel)
     out = torch.empty_like(vel)
     ws = _workspace(1, B, nx, ny, vel.device)
@@ -68,6 +102,12 @@ def update_velocity(vel, pres, dt, dx, compat=True):
 def update_pressure(pres, vel, dt, dx):
     _check("update_pressure", pres, vel)
     pres, vel = pres.contiguous(), vel.contiguous()
+    if _wants_grad(pres, vel):
+        return _UpdatePressure.apply(pres, vel, float(dt), float(dx))
+    return _update_pressure(pres, vel, dt, dx)
+
+
+def _update_pressure(pres, vel, dt, dx):
     B, nx, ny = _geo(pres)
     out = torch.empty_like(pres)
     check(lib.bpk_ns_update_pressure_f32(pres.data_ptr(), vel.data_ptr(), out.data_ptr(), B, nx,
@@ -79,9 +119,25 @@ def update_pressure(pres, vel, dt, dx):
 def full_step(dens, vel, pres, dt, dx, compat=True, out=None):
     """One simulator step (pinn_kalman/simulator.py:55-57) in two fused launches:
     vel' = update_velocity(vel, pres); pres' = update_pressure(pres, vel');
-    dens' = update_density(dens, vel').  Bit-identical to the three calls."""
+    dens' = update_density(dens, vel').  Bit-identical to the three calls.
+
+    compat=False is differentiable to first order when grad mode is on and an input requires
+    grad (backward: csrc/ns_step_vjp.hip; sgn(u), sgn(v) and the upwind indices are constants
+    of the derivative); the forward launches and their results are the same with and without
+    a graph.  `out=` buffers cannot be saved for backward, so `out=` with a required gradient
+    raises.  compat=True is unchanged in every respect: the reference's forward-only op, it
+    builds no autograd graph (its cross-sample plane mixing is a quirk nobody differentiates)."""
     _check("full_step", dens, vel, pres)
     dens, vel, pres = dens.contiguous(), vel.contiguous(), pres.contiguous()
+    if not compat and _wants_grad(dens, vel, pres):
+        if out is not None:
+            raise RuntimeError("ns_step.full_step: out= buffers cannot be saved for backward; "
+                               "drop out= or call under torch.no_grad()")
+        return _FullStep.apply(dens, vel, pres, float(dt), float(dx))
+    return _full_step(dens, vel, pres, dt, dx, compat, out)
+
+
+def _full_step(dens, vel, pres, dt, dx, compat, out):
     B, nx, ny = _geo(dens)
     if out is None:
         out = (torch.empty_like(dens), torch.empty_like(vel), torch.empty_like(pres))
@@ -91,6 +147,154 @@ def full_step(dens, vel, pres, dt, dx, compat=True, out=None):
                                    float(dx), int(bool(compat)), stream_ptr(dens.device)),
           "ns_step.full_step")
     return d1, v1, p1
+
+
+# ---- autograd (compat=False): the forward is the launch above, the backward the gather
+# adjoints of csrc/ns_step_vjp.hip.  First order only, in the manner of torch's
+# once_differentiable but stricter: that decorator arms its error only when a cotangent
+# requires grad, so torch.autograd.grad(..., create_graph=True) followed by a backward
+# through the gradient would silently drop this op's second-order term.  Here every gradient
+# produced under create_graph carries a node that raises when it is differentiated.
+class _NoDoubleBackward(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, what, *grads):
+        ctx.what = what
+        return tuple(g.view_as(g) for g in grads)
+
+    @staticmethod
+    def backward(ctx, *_):
+        raise RuntimeError(f"{ctx.what}: double backward is not supported -- the backward is a "
+                           "hand-written first-order HIP adjoint (once differentiable)")
+
+
+def once_differentiable(what):
+    def deco(fn):
+        @functools.wraps(fn)
+        def wrapper(ctx, *cots):
+            create_graph = torch.is_grad_enabled()
+            with torch.no_grad():
+                outs = fn(ctx, *cots)
+            if not create_graph:
+                return outs
+            outs = list(outs)
+            idx = [i for i, o in enumerate(outs) if o is not None]
+            if idx:
+                armed = _NoDoubleBackward.apply(
+                    what, *[outs[i].detach().requires_grad_(True) for i in idx])
+                for i, o in zip(idx, armed):
+                    outs[i] = o
+            return tuple(outs)
+        return wrapper
+    return deco
+
+
+class _UpdateDensity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dens, vel, dt, dx):
+        ctx.save_for_backward(dens, vel)
+        ctx.dt, ctx.dx = dt, dx
+        return _update_density(dens, vel, dt, dx)
+
+    @staticmethod
+    @once_differentiable("ns_step.update_density")
+    def backward(ctx, g):
+        dens, vel = ctx.saved_tensors
+        B, nx, ny = _geo(dens)
+        g = _cot(g)
+        g_dens = torch.empty_like(dens) if ctx.needs_input_grad[0] else None
+        g_vel = torch.empty_like(vel) if ctx.needs_input_grad[1] else None
+        ws = _vjp_workspace(0, B, nx, ny, dens.device)
+        check(lib.bpk_ns_update_density_vjp_f32(dens.data_ptr(), vel.data_ptr(), g.data_ptr(),
+                                                ptr(g_dens), None, ptr(g_vel), ws.data_ptr(), B,
+                                                nx, ny, ctx.dt, ctx.dx, stream_ptr(dens.device)),
+              "ns_step.update_density backward")
+        return g_dens, g_vel, None, None
+
+
+class _UpdatePressure(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pres, vel, dt, dx):
+        ctx.save_for_backward(vel)
+        ctx.dt, ctx.dx = dt, dx
+        return _update_pressure(pres, vel, dt, dx)
+
+    @staticmethod
+    @once_differentiable("ns_step.update_pressure")
+    def backward(ctx, g):
+        vel, = ctx.saved_tensors
+        B, nx, ny = _geo(vel)
+        g = _cot(g)
+        g_pres = torch.empty_like(g) if ctx.needs_input_grad[0] else None
+        g_vel = torch.empty_like(vel) if ctx.needs_input_grad[1] else None
+        check(lib.bpk_ns_update_pressure_vjp_f32(vel.data_ptr(), g.data_ptr(), ptr(g_pres), None,
+                                                 ptr(g_vel), B, nx, ny, ctx.dt, ctx.dx,
+                                                 stream_ptr(vel.device)),
+              "ns_step.update_pressure backward")
+        return g_pres, g_vel, None, None
+
+
+class _UpdateVelocity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vel, pres, dt, dx):
+        ctx.save_for_backward(vel, pres)
+        ctx.dt, ctx.dx = dt, dx
+        return _update_velocity(vel, pres, dt, dx, False)
+
+    @staticmethod
+    @once_differentiable("ns_step.update_velocity")
+    def backward(ctx, g):
+        vel, pres = ctx.saved_tensors
+        B, nx, ny = _geo(vel)
+        g = _cot(g)
+        g_vel = torch.empty_like(vel)  # the pressure gradient is computed from it
+        g_pres = torch.empty_like(pres) if ctx.needs_input_grad[1] else None
+        ws = _vjp_workspace(1, B, nx, ny, vel.device)
+        check(lib.bpk_ns_update_velocity_vjp_f32(vel.data_ptr(), pres.data_ptr(), g.data_ptr(),
+                                                 g_vel.data_ptr(), ptr(g_pres), ws.data_ptr(), B,
+                                                 nx, ny, ctx.dt, ctx.dx, stream_ptr(vel.device)),
+              "ns_step.update_velocity backward")
+        return (g_vel if ctx.needs_input_grad[0] else None), g_pres, None, None
+
+
+class _FullStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dens, vel, pres, dt, dx):
+        d1, v1, p1 = _full_step(dens, vel, pres, dt, dx, False, None)
+        ctx.save_for_backward(dens, vel, pres, v1)
+        ctx.set_materialize_grads(False)  # an unused output's cotangent stays None
+        ctx.dt, ctx.dx = dt, dx
+        return d1, v1, p1
+
+    @staticmethod
+    @once_differentiable("ns_step.full_step")
+    def backward(ctx, g_d1, g_v1, g_p1):
+        dens, vel, pres, v1 = ctx.saved_tensors
+        B, nx, ny = _geo(dens)
+        g_d1, g_v1, g_p1 = _cot(g_d1), _cot(g_v1), _cot(g_p1)
+        if g_d1 is None and g_v1 is None and g_p1 is None:
+            return None, None, None, None, None
+        need = ctx.needs_input_grad
+        st = stream_ptr(dens.device)
+        if not (need[1] or need[2]):  # dens' is the only output that depends on dens
+            if g_d1 is None:
+                return None, None, None, None, None
+            g_dens = torch.empty_like(dens)
+            ws = _vjp_workspace(0, B, nx, ny, dens.device)
+            check(lib.bpk_ns_update_density_vjp_f32(dens.data_ptr(), v1.data_ptr(),
+                                                    g_d1.data_ptr(), g_dens.data_ptr(), None,
+                                                    None, ws.data_ptr(), B, nx, ny, ctx.dt,
+                                                    ctx.dx, st), "ns_step.full_step backward")
+            return g_dens, None, None, None, None
+        g_dens = torch.empty_like(dens) if need[0] else None
+        # velocity and pressure gradients come out of one pass over the velocity stage
+        g_vel, g_pres = torch.empty_like(vel), torch.empty_like(pres)
+        ws = _vjp_workspace(3, B, nx, ny, dens.device)
+        check(lib.bpk_ns_full_step_vjp_f32(dens.data_ptr(), vel.data_ptr(), pres.data_ptr(),
+                                           v1.data_ptr(), ptr(g_d1), ptr(g_v1), ptr(g_p1),
+                                           ptr(g_dens), g_vel.data_ptr(), g_pres.data_ptr(),
+                                           ws.data_ptr(), B, nx, ny, ctx.dt, ctx.dx, st),
+              "ns_step.full_step backward")
+        return g_dens, (g_vel if need[1] else None), (g_pres if need[2] else None), None, None
 
 
 # low-level kernels (one launch each), exposed for tests and custom pipelines

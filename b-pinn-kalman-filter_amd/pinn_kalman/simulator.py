@@ -43,6 +43,21 @@ def simulate(model, begin, t_range=(0, 100), stride=1):
     return result, vel
 
 
+def rollout(f, v, p, steps, dt=dt, dx=dx, compat=False):
+    """`steps` simulator steps from density f [B, 1, H, W], velocity v [B, 2, H, W] and
+    pressure p [B, 1, H, W] -> stacked trajectories ([steps, B, 1, H, W], [steps, B, 2, H, W],
+    [steps, B, 1, H, W]); entry k is the state after k + 1 steps.  With compat=False the
+    rollout is differentiable with respect to f, v and p (`ns_step.full_step`'s HIP adjoint);
+    compat=True is the reference's forward-only step and carries no graph."""
+    fs, vs, ps = [], [], []
+    for _ in range(int(steps)):
+        f, v, p = ns_step.full_step(f, v, p, dt, dx, compat=compat)
+        fs.append(f)
+        vs.append(v)
+        ps.append(p)
+    return torch.stack(fs), torch.stack(vs), torch.stack(ps)
+
+
 def step(model, begin, t_range=(0, 100), stride=1, replicas=256, device=None, ctx=None,
          compat=True):
     """ns_step rollout of `replicas` copies of snapshot t_range[0]; velocity channels are

@@ -222,6 +222,46 @@ int bpk_ns_full_step_f32(const float* dens, const float* vel, const float* pres,
                          float* vel_out, float* pres_out, void* workspace, int B, int nx, int ny,
                          float dt, float dx, int compat, void* stream);
 
+/* Vector-Jacobian products of the step with compat = 0 (csrc/ns_step_vjp.hip): plain
+ * float32 gather adjoints, no atomics, bit-reproducible.  sgn(u), sgn(v) and the upwind
+ * indices are constants of the derivative.  Velocity tensors are 2B planes (u, v of sample
+ * b at 2b / 2b+1), everything else B contiguous planes; nx, ny >= 2 as in the forward.
+ * Scratch: bpk_ns_vjp_workspace_bytes(op, B, nx, ny) bytes (op: 0 = update_density,
+ * 1 = update_velocity, 2 = update_pressure (none), 3 = full_step).
+ *
+ * gradient_vjp: out = base (optional) + scale * (Dx^T gx + Dy^T gy); out may alias base.
+ * cip_vjp: one CIP advection out = CIP(f; vel) with stencil gradients fx, fy given as
+ *   independent inputs.  g_f / g_fx / g_fy (all three or none): cotangents of f, fx, fy.
+ *   g_vel (optional, needs f, fx, fy): g_vel_in (optional, may alias g_vel) + the
+ *   cotangent of vel.
+ * update_*_vjp: the backward of the op of that name; an output pointer that is NULL is not
+ *   computed.  g_vel = g_vel_in (optional, may alias) + the op's own velocity cotangent.
+ * full_step_vjp: cotangents g_dens1 / g_vel1 / g_pres1 of the three outputs (each
+ *   optional, at least one), vel1 = the step's velocity output; writes g_vel, g_pres
+ *   (required) and g_dens (optional). */
+int64_t bpk_ns_vjp_workspace_bytes(int op, int B, int nx, int ny);
+int bpk_ns_gradient_vjp_f32(const float* gx, const float* gy, const float* base, float* out, int B,
+                            int nx, int ny, float dx, float scale, void* stream);
+int bpk_ns_cip_vjp_f32(const float* f, int64_t f_plane_stride, const float* fx, const float* fy,
+                       const float* vel, const float* g_out, float* g_f, float* g_fx, float* g_fy,
+                       const float* g_vel_in, float* g_vel, int B, int nx, int ny, float dt,
+                       float dx, void* stream);
+int bpk_ns_update_density_vjp_f32(const float* dens, const float* vel, const float* g_out,
+                                  float* g_dens, const float* g_vel_in, float* g_vel,
+                                  void* workspace, int B, int nx, int ny, float dt, float dx,
+                                  void* stream);
+int bpk_ns_update_pressure_vjp_f32(const float* vel, const float* g_out, float* g_pres,
+                                   const float* g_vel_in, float* g_vel, int B, int nx, int ny,
+                                   float dt, float dx, void* stream);
+int bpk_ns_update_velocity_vjp_f32(const float* vel, const float* pres, const float* g_out,
+                                   float* g_vel, float* g_pres, void* workspace, int B, int nx,
+                                   int ny, float dt, float dx, void* stream);
+int bpk_ns_full_step_vjp_f32(const float* dens, const float* vel, const float* pres,
+                             const float* vel1, const float* g_dens1, const float* g_vel1,
+                             const float* g_pres1, float* g_dens, float* g_vel, float* g_pres,
+                             void* workspace, int B, int nx, int ny, float dt, float dx,
+                             void* stream);
+
 /* ------------------------------------------------------------------------- *
  * GroupNorm (+ optional fused per-(n,c) bias before the norm and SiLU after).
  * The build's fusion of nn.GroupNorm + act + `h += Dense(temb)[:, :, None, None]`
