@@ -936,6 +936,40 @@ int bpk_blur2d_adjoint_f32(const float* y, float* out, int64_t planes, int H, in
 int bpk_blur2d_adjoint_f64(const double* y, double* out, int64_t planes, int H, int W,
                            const double* taps, int K, int stride, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * letkf: analysis step of the local ensemble transform Kalman filter (Hunt, Kostelich &
+ * Szunyogh 2007) for an identity observation of the state, float32.  No counterpart in the
+ * reference (it has no ensemble filter); the truth is the float64 restatement of these
+ * equations in tests/letkf_ref.py.
+ *   ens   [B, m, C, H, W]  background ensemble, 2 <= m <= 64, 1 <= C <= 8
+ *   obs   [B, C, H, W]     observation in state space
+ *   prec  [B, C, H, W]     inverse observation variances, 0 = unobserved
+ *   taper [2R+1, 2R+1]     localization weights of the window (device memory), 0 <= R <= 8
+ *   ens_out [B, m, C, H, W], status int32 [B, H, W]
+ * For every (b, y0, x0), over the window |y - y0| <= R, |x - x0| <= R clipped at the domain
+ * edge (no wrap), with xbar the member mean, dX_k = ens_k - xbar and
+ * rho_j = taper[y - y0 + R, x - x0 + R] * prec_j for the window entry j = (c, y, x):
+ *   A  = (m-1)/inflation I + sum_j rho_j dX_j dX_j^T        (m x m, dX_j across the members)
+ *   g  = sum_j rho_j dX_j (obs_j - xbar_j)
+ *   A  = Q L Q^T                                            (cyclic Jacobi, at most 16 sweeps)
+ *   wbar = Q L^-1 Q^T g,   Wa = sqrt(m-1) Q L^-1/2 Q^T      (the symmetric root)
+ *   ens_out[i, c, y0, x0] = xbar_c + sum_k dX_k[c, y0, x0] (wbar_k + Wa[k, i])
+ * An entry with rho_j == 0 is skipped, not multiplied in: obs may hold anything (NaN
+ * included) where prec == 0.  status is 1 where the eigen-iteration reached its sweep cap or
+ * the result is not finite; ens_out there is the background with its perturbations scaled by
+ * sqrt(inflation).  Elsewhere status is 0.
+ * ens_out must not alias ens (neighbouring grid points read the background).
+ * `workspace`: bpk_letkf_workspace_bytes(B, m, C, H, W) bytes (the member mean and the
+ * perturbations, member-innermost); the query returns -1 for sizes out of range.
+ * Arguments are validated before any device call.  Two launches, no atomics, every
+ * reduction in a fixed order (bit-reproducible), asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+int64_t bpk_letkf_workspace_bytes(int64_t B, int m, int C, int H, int W);
+int bpk_letkf_analysis_f32(const float* ens, const float* obs, const float* prec,
+                           const float* taper, float* ens_out, int* status, void* workspace,
+                           int64_t B, int m, int C, int H, int W, int R, float inflation,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
