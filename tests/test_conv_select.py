@@ -163,3 +163,45 @@ def test_local_choice_does_not_short_circuit_a_later_spmd_call():
     for r in res:
         assert r[2] is None, r[2]
     assert [r[1] for r in res] == [1, 1]  # rank 0's SPMD timing, agreed
+
+
+def test_undecided_key_under_capture_runs_candidate_0_and_caches_nothing(monkeypatch):
+    """Stream capture cannot time: `_decide` answers None for a key never decided eagerly,
+    `_pick_any` then runs the first candidate, and nothing is cached or written, so the first
+    eager call of the key still times it."""
+    from op import conv
+    monkeypatch.setattr(conv, "_TABLE_PATH", None)
+    monkeypatch.setattr(conv, "_TABLE", {})
+    monkeypatch.setattr(conv, "_CHOICE", {})
+    monkeypatch.setattr(conv, "_CHOICE_LOCAL", {})
+    monkeypatch.setattr(conv, "_PICK_FIRST", False)
+    monkeypatch.setattr(conv.torch.cuda, "is_current_stream_capturing", lambda: True)
+
+    def no_timer(*a, **k):
+        raise AssertionError("timed a candidate under stream capture")
+    monkeypatch.setattr(conv, "_time_us", no_timer)
+    key = ("f3", (2, 8, 8, 16), (16, 8, 3, 3), False, False)
+    assert conv._decide(key, [_never, _never]) is None
+    assert conv._pick_any(key, [lambda: "first", lambda: "second"]) == "first"
+    with conv.local_choices():
+        assert conv._pick_any(key, [lambda: "first", lambda: "second"]) == "first"
+    assert conv._CHOICE == {} and conv._CHOICE_LOCAL == {} and conv._TABLE == {}
+
+
+def test_eager_choice_is_replayed_under_capture(monkeypatch):
+    """A key decided by an eager call keeps its candidate inside a capture (no timer there)."""
+    from op import conv
+    monkeypatch.setattr(conv, "_TABLE_PATH", None)
+    monkeypatch.setattr(conv, "_TABLE", {})
+    monkeypatch.setattr(conv, "_CHOICE", {})
+    monkeypatch.setattr(conv, "_PICK_FIRST", False)
+    capturing = [False]
+    monkeypatch.setattr(conv.torch.cuda, "is_current_stream_capturing", lambda: capturing[0])
+    times = iter([7.0, 2.0])
+    monkeypatch.setattr(conv, "_time_us", lambda f: next(times))
+    key = ("w3", (2, 32, 8, 16), (48, 32, 3, 3))
+    assert conv._pick_any(key, [lambda: "first", lambda: "second"]) == "second"
+    capturing[0] = True  # `times` is used up: a second timing would raise StopIteration
+    assert conv._decide(key, [_never, _never]) == 1
+    assert conv._pick_any(key, [lambda: "first", lambda: "second"]) == "second"
+    assert conv._CHOICE == {key: 1}

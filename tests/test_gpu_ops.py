@@ -4,11 +4,21 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import load_golden
+import conv_pick
+from conftest import load_golden, record_err
 from oracle import fused_act_ref, grid_sample_ref, ns_step_ref
 from oracle.upfirdn2d_ref import upfirdn2d_np
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def _first_conv_candidate(monkeypatch):
+    """Every timed kernel choice of op.conv (tests/conv_pick.py) runs its first candidate in
+    this module -- the kernel the tests' names and docstrings speak of -- with no timing and no
+    choice inherited from an earlier test; tests that name a candidate force it themselves.
+    Both candidates of every choice against float64: tests/test_gpu_conv_pick.py."""
+    conv_pick.first_only(monkeypatch)
 
 
 # ------------------------------------------------------------------ upfirdn2d
@@ -384,18 +394,26 @@ def test_conv3x3_winograd_matches_fp32_reference(hip, N, cin, cout, hw, with_bia
     assert (mi - ref).abs().max().item() <= 2e-5 * scale
 
 
-@pytest.mark.parametrize("cin", [16, 64])
-def test_conv3x3_winograd_backward_and_filter_cache(hip, cin):
-    """gradients vs MIOpen's; cin = 64 takes the Winograd backward-data path (the forward
-    conv of gy with the flipped, transposed filter), cin = 16 the MIOpen fallback."""
+@pytest.mark.parametrize("cin,candidate", [
+    pytest.param(16, 0, id="16"), pytest.param(64, 0, id="64"),
+    pytest.param(16, 1, id="16-igemm"), pytest.param(64, 1, id="64-igemm")])
+def test_conv3x3_winograd_backward_and_filter_cache(hip, monkeypatch, cin, candidate):
+    """gradients vs MIOpen's, with the timed choices forced (tests/conv_pick.py): at 16 x 32 the
+    forward is the site f3 and the backward-data conv (the conv of gy with the flipped,
+    transposed filter) the site d3, for both cin; the weight gradient is the site w3 for
+    cin = 64 and the implicit GEMM alone for cin = 16 (the Winograd weight gradient takes
+    multiples of 32).  candidate 0: the Winograd kernels, 1: the implicit-GEMM ones."""
     import torch.nn.functional as F
     from op.conv import conv3x3
+    log = conv_pick.forced(monkeypatch, {"f3": candidate, "d3": candidate, "w3": candidate})
     g = torch.Generator().manual_seed(1)
     x = torch.randn(2, cin, 16, 32, generator=g).to(hip).requires_grad_()
     w = (torch.randn(128, cin, 3, 3, generator=g) * 0.1).to(hip).requires_grad_()
     b = torch.randn(128, generator=g).to(hip).requires_grad_()
     go = torch.randn(2, 128, 16, 32, generator=g).to(hip)
     gx, gw, gb = torch.autograd.grad(conv3x3(x, w, b), (x, w, b), go)
+    assert conv_pick.reached(log, "f3") and conv_pick.reached(log, "d3")
+    assert bool(conv_pick.reached(log, "w3")) == (cin == 64)
     rx, rw, rb = torch.autograd.grad(F.conv2d(x, w, b, padding=1), (x, w, b), go)
     for a, r in ((gx, rx), (gw, rw), (gb, rb)):
         assert (a - r).abs().max().item() <= 3e-5 * r.abs().max().item()
@@ -445,11 +463,10 @@ def test_conv3x3_winograd_weight_gradient(hip, N, cin, cout, h, w):
     del F
 
 
-def test_conv3x3_winograd_fused_residual_tail(hip):
-    """conv3x3(h, w, b, skip=x, div) == residual_rescale(x, conv3x3(h, w), b, div) bit for bit
-    (same epilogue arithmetic), and its gradients match the unfused composition."""
+def _fused_residual_tail_case(hip, monkeypatch, candidate):
     from op.conv import conv3x3
     from op.norm_act import residual_rescale
+    log = conv_pick.forced(monkeypatch, {"f3": candidate, "d3": candidate, "w3": candidate})
     g = torch.Generator().manual_seed(3)
     h = torch.randn(2, 64, 16, 32, generator=g).to(hip).requires_grad_()
     w = (torch.randn(64, 64, 3, 3, generator=g) * 0.05).to(hip).requires_grad_()
@@ -458,12 +475,34 @@ def test_conv3x3_winograd_fused_residual_tail(hip):
     div = float(np.sqrt(2.0))
     fused = conv3x3(h, w, b, skip=x, div=div)
     plain = residual_rescale(x, conv3x3(h, w), b, div)
+    xs, ws = (2, 64, 16, 32), (64, 64, 3, 3)  # (bias, skip) are in the key: two keys
+    assert conv_pick.reached(log, "f3") == [("f3", xs, ws, True, True), ("f3", xs, ws, False, False)]
     assert torch.equal(fused, plain)
     go = torch.randn_like(fused)
     g1 = torch.autograd.grad(fused, (h, w, b, x), go)
     g2 = torch.autograd.grad(plain, (h, w, b, x), go)
     for a, r in zip(g1, g2):
         assert (a - r).abs().max().item() <= 1e-5 * max(1.0, r.abs().max().item())
+
+
+def test_conv3x3_winograd_fused_residual_tail(hip, monkeypatch):
+    """conv3x3(h, w, b, skip=x, div) == residual_rescale(x, conv3x3(h, w), b, div) bit for bit
+    (same epilogue arithmetic), and its gradients match the unfused composition -- with the
+    Winograd kernel (candidate 0 of the site f3) for both calls.  The two calls are two keys of
+    the timed choice ((bias, skip) are part of the key), decided independently when nothing
+    forces them: only equal choices are comparable bit for bit, a Winograd result and an
+    implicit-GEMM one are not."""
+    _fused_residual_tail_case(hip, monkeypatch, 0)
+
+
+def test_conv3x3_igemm_residual_tail_bit_identical_to_unfused(hip, monkeypatch):
+    """The same with the implicit-GEMM kernel (candidate 1) for both keys.  Equality holds here
+    too: the kernel adds the bias to the finished K sum in one fp32 addition (in its epilogue,
+    or in the split-K reduce; the split count does not depend on the bias), so the fused call is
+    residual_rescale(x, acc + b, None, div) = (x + ((acc + b) + 0)) / div and the unfused one
+    residual_rescale(x, acc, b, div) = (x + (acc + b)) / div from the same launch of the same
+    kernel on the same operands."""
+    _fused_residual_tail_case(hip, monkeypatch, 1)
 
 
 def test_conv3x3_winograd_fused_groupnorm_silu_prologue(hip):
@@ -944,16 +983,27 @@ def test_skip_link_hands_the_skip_gradient_to_the_groupnorm_backward(hip, kind):
     assert nl == nu - 1, (nl, nu)
 
 
-@pytest.mark.parametrize("kind,cin,cout,hw", [("biggan", 128, 128, 32), ("biggan", 128, 256, 8),
-                                              ("ddpm", 128, 128, 32), ("ddpm", 256, 128, 16)])
-def test_gn_silu_conv_under_autograd_matches_unfused(hip, kind, cin, cout, hw):
+_GN_AD_SHAPES = [("biggan", 128, 128, 32), ("biggan", 128, 256, 8), ("ddpm", 128, 128, 32),
+                 ("ddpm", 256, 128, 16)]
+
+
+@pytest.mark.parametrize("kind,cin,cout,hw,candidate", [
+    pytest.param(*c, cand, id="-".join(str(v) for v in c) + ("-igemm" if cand else ""))
+    for cand in (0, 1) for c in _GN_AD_SHAPES])
+def test_gn_silu_conv_under_autograd_matches_unfused(hip, monkeypatch, kind, cin, cout, hw,
+                                                     candidate):
     """The residual blocks in eval mode under autograd (DPS) with GroupNorm+SiLU inside the
     Winograd convs' input loads (op.conv.gn_silu_conv3x3_ad; 8x8 images on the pair form) ==
     the unfused composition (GroupNorm+SiLU kernel, conv, residual): output, d/dx and every
-    parameter gradient (the weight gradient with the prologue in its patch load) within 2e-5
-    of the tensor's max; and d/dx alone (the DPS call: torch.autograd.grad w.r.t. the input,
-    no weight gradients computed)."""
+    parameter gradient within 2e-5 of the tensor's max; and d/dx alone (the DPS call:
+    torch.autograd.grad w.r.t. the input, no weight gradients computed).  All four images are
+    small (H * W <= 32 x 32), so the backward of the fused form goes through the timed choices
+    d3 (the activation's gradient) and w3 (the weight gradient on the materialised activation;
+    the prologue in the weight gradient's patch load is for larger images), and the unfused
+    composition through f3, d3 and w3; `candidate` forces all of them (tests/conv_pick.py): 0
+    the Winograd kernels, 1 the implicit-GEMM ones."""
     import models.layers as layers
+    log = conv_pick.forced(monkeypatch, {"f3": candidate, "d3": candidate, "w3": candidate})
     import models.layerspp as lpp
     torch.manual_seed(0)
     if kind == "biggan":
@@ -988,7 +1038,10 @@ def test_gn_silu_conv_under_autograd_matches_unfused(hip, kind, cin, cout, hw):
             layers._GN_CONV_AD = old
         return y.detach(), x.grad, grads, gx_only
     yf, gxf, gpf, gof = run(True)
+    assert conv_pick.reached(log, "d3") and conv_pick.reached(log, "w3")
+    assert not conv_pick.reached(log, "f3")  # the fused forward has no choice
     yu, gxu, gpu_, gou = run(False)
+    assert conv_pick.reached(log, "f3")
 
     def close(a, b, what):
         scale = b.abs().max().item()
@@ -1415,20 +1468,25 @@ def test_conv2d_wgrad_small_cout_vs_fp64(hip, case):
     assert none is None and torch.equal(dw2, dw)
 
 
-@pytest.mark.parametrize("cin", [1, 4])
+@pytest.mark.parametrize("cin", [1, 4, 2, 3])
 def test_conv2d_input_select_small_cin_candidates(hip, cin, monkeypatch):
-    """Backward-data into <= 4 channels: both candidates of the timed choice (the small-Cout
-    kernel on the flipped / transposed filter, and igemm) vs float64 conv2d_input."""
+    """Backward-data into <= 4 channels (the site dsc, at an odd batch): both candidates of the
+    timed choice (the small-Cout kernel on the flipped / transposed filter, and igemm), forced
+    and asserted as reached (tests/conv_pick.py), vs float64 conv2d_input."""
     from op import conv
     g = torch.Generator().manual_seed(cin)
     xshape = (3, cin, 16, 20)
+    assert (3, cin, 64, 16, 20) in conv_pick.DSC_CASES
     w = torch.randn(64, cin, 3, 3, generator=g) / 24
     gy = torch.randn(3, 64, 16, 20, generator=g)
     ref = torch.nn.grad.conv2d_input(xshape, w.double(), gy.double(), 1, 1)
     for c in (0, 1):
-        monkeypatch.setattr(conv, "_CHOICE", {("dsc", xshape, tuple(w.shape), (1, 1), (1, 1)): c})
+        log = conv_pick.forced(monkeypatch, {"dsc": c})
         got = conv.conv2d_input_select(xshape, w.to(hip), gy.to(hip), 1, 1)
+        assert conv_pick.reached(log, "dsc") == [("dsc", xshape, tuple(w.shape), (1, 1), (1, 1))]
+        assert len(log) == 1
         err = float((got.double().cpu() - ref).abs().max())
+        record_err(f"conv_pick dsc[{c}] {xshape}", err, 2e-5 * max(1.0, float(ref.abs().max())))
         assert err <= 2e-5 * max(1.0, float(ref.abs().max())), (c, err)
 
 

@@ -16,7 +16,18 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_pick
+
 gpu = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def _first_conv_candidate(monkeypatch):
+    """Every timed kernel choice of op.conv (tests/conv_pick.py) runs its first candidate in
+    this module -- the Winograd kernels of the blocks -- with no timing and no choice
+    inherited from an earlier test.  Both candidates of every choice against float64:
+    tests/test_gpu_conv_pick.py."""
+    conv_pick.first_only(monkeypatch)
 RTOL = 1e-5
 K1D = np.array([1.0, 3.0, 3.0, 1.0])
 
