@@ -21,106 +21,9 @@
 // Plain float32 with FMA contraction; none of the forward's exact-division machinery.
 // A velocity component exactly 0 makes the forward non-finite (a reference property); the
 // backward there is unspecified, but sgn = 0 gives xm = x, so every index stays in bounds.
-#include <algorithm>
-
-#include "bpk_common.h"
+#include "ns_cip_deriv.h"  // Geo, VjpConst, clampx, sgn, NS_VJP_SITES, grid_for, cip_weights, cip_dxy
 
 namespace {
-
-struct Geo {
-  int nx, ny;
-  int64_t hw;
-};
-
-struct VjpConst {
-  float dt, dx, r1, r2, r3;  // 1/dx, 1/dx^2, 1/dx^3
-  __device__ VjpConst(float dt_, float dx_) : dt(dt_), dx(dx_) {
-    r1 = 1.0f / dx;
-    r2 = r1 * r1;
-    r3 = r2 * r1;
-  }
-};
-
-__device__ inline int clampx(int x, int n) { return x < 0 ? -x : (x > n - 1 ? 2 * n - 2 - x : x); }
-
-__device__ inline int sgn(float v) { return v < 0.0f ? -1 : (v > 0.0f ? 1 : 0); }
-
-// One thread per site, x fastest: blockIdx.y walks the planes and blockIdx.x the sites of a
-// plane, so no thread pays a 64-bit division to find its plane.  Closes with one brace.
-#define NS_VJP_SITES(planes)                                                      \
-  for (int64_t b = blockIdx.y; b < (planes); b += gridDim.y)                      \
-    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < (int)g.hw;            \
-         s += gridDim.x * blockDim.x)
-
-// d out / d (gathered value) of one CIP site, from the site's velocity alone
-struct CipW {
-  float f_c, f_xm, f_ym, f_xy;
-  float fx_c, fx_xm, fx_ym;
-  float fy_c, fy_xm, fy_ym;
-};
-
-// out = a X^3 + c X^2 Y + e X^2 + g X Y + fx_c X + b Y^3 + d X Y^2 + f Y^2 + fy_c Y + f_c
-// with (ns_step.hip cip_site_fast; 1/s = s for s = +-1)
-//   a = (sx (fx_xm + fx_c) dx + 2 tmp2) sx / dx^3     b = (sy (fy_ym + fy_c) dx + 2 tmp3) sy / dx^3
-//   c = (-tmp1 - sx (fx_ym - fx_c) dx) sy / dx^3      d = (-tmp1 - sy (fy_xm - fy_c) dx) sx / dx^3
-//   e = (3 tmp2 + sx (fx_xm + 2 fx_c) dx) / dx^2      f = (3 tmp3 + sy (fy_ym + 2 fy_c) dx) / dx^2
-//   g = (-(fy_xm - fy_c) + c dx^2) sx / dx
-//   tmp1 = f_c - f_ym - f_xm + f_xy,  tmp2 = f_xm - f_c,  tmp3 = f_ym - f_c
-__device__ inline CipW cip_weights(float u, float v, int sxi, int syi, const VjpConst& k) {
-  const float sx = (float)sxi, sy = (float)syi;
-  const float X = -u * k.dt, Y = -v * k.dt;
-  const float XY = X * Y;
-  const float wg = XY;                                  // d out / d g
-  const float wa = X * X * X * sx * k.r3;               // cotangent of a's numerator
-  const float wb = Y * Y * Y * sy * k.r3;
-  const float wc = (X * XY + wg * k.dx * sx) * sy * k.r3;  // c feeds g as well
-  const float wd = XY * Y * sx * k.r3;
-  const float we = X * X * k.r2;
-  const float wf = Y * Y * k.r2;
-  const float t1 = -(wc + wd);
-  const float t2 = 2.0f * wa + 3.0f * we;
-  const float t3 = 2.0f * wb + 3.0f * wf;
-  const float gs = wg * sx * k.r1;
-  const float sxd = sx * k.dx, syd = sy * k.dx;
-  CipW w;
-  w.f_c = 1.0f + t1 - t2 - t3;
-  w.f_xm = t2 - t1;
-  w.f_ym = t3 - t1;
-  w.f_xy = t1;
-  w.fx_xm = sxd * (wa + we);
-  w.fx_c = sxd * (wa + wc + 2.0f * we) + X;
-  w.fx_ym = -sxd * wc;
-  w.fy_ym = syd * (wb + wf);
-  w.fy_c = syd * (wb + wd + 2.0f * wf) + Y + gs;
-  w.fy_xm = -syd * wd - gs;
-  return w;
-}
-
-// (d out / dX, d out / dY) of one CIP site from its ten gathered values
-__device__ inline void cip_dxy(const float* __restrict__ f, const float* __restrict__ fx,
-                               const float* __restrict__ fy, int x, int y, float u, float v,
-                               const Geo& g, const VjpConst& k, float* dX, float* dY) {
-  const int sxi = sgn(u), syi = sgn(v);
-  const int xm = clampx(x - sxi, g.nx), ym = clampx(y - syi, g.ny);
-  const int64_t c = (int64_t)y * g.nx + x, cxm = (int64_t)y * g.nx + xm,
-                cym = (int64_t)ym * g.nx + x, cxy = (int64_t)ym * g.nx + xm;
-  const float sx = (float)sxi, sy = (float)syi;
-  const float f_c = f[c], f_xm = f[cxm], f_ym = f[cym], f_xy = f[cxy];
-  const float fx_c = fx[c], fx_xm = fx[cxm], fx_ym = fx[cym];
-  const float fy_c = fy[c], fy_xm = fy[cxm], fy_ym = fy[cym];
-  const float tmp1 = f_c - f_ym - f_xm + f_xy;
-  const float tmp2 = f_xm - f_c, tmp3 = f_ym - f_c;
-  const float a = (sx * (fx_xm + fx_c) * k.dx + 2.0f * tmp2) * sx * k.r3;
-  const float b = (sy * (fy_ym + fy_c) * k.dx + 2.0f * tmp3) * sy * k.r3;
-  const float cc = (-tmp1 - sx * (fx_ym - fx_c) * k.dx) * sy * k.r3;
-  const float d = (-tmp1 - sy * (fy_xm - fy_c) * k.dx) * sx * k.r3;
-  const float e = (3.0f * tmp2 + sx * (fx_xm + 2.0f * fx_c) * k.dx) * k.r2;
-  const float ff = (3.0f * tmp3 + sy * (fy_ym + 2.0f * fy_c) * k.dx) * k.r2;
-  const float gg = (-(fy_xm - fy_c) + cc * k.dx * k.dx) * sx * k.r1;
-  const float X = -u * k.dt, Y = -v * k.dt;
-  *dX = (3.0f * a * X + 2.0f * cc * Y + 2.0f * e) * X + (gg + d * Y) * Y + fx_c;
-  *dY = (3.0f * b * Y + 2.0f * d * X + 2.0f * ff) * Y + (gg + cc * X) * X + fy_c;
-}
 
 // NF fields advected by the same velocity (planes 2b, 2b + 1 of `vel`).  Field j of sample b:
 // f[j] + b * fstride, its stencil gradient fx[j] / fy[j] and the outputs gf[j] / gfx[j] /
@@ -307,12 +210,6 @@ __global__ __launch_bounds__(256) void k_grad_vjp(const float* gx, int64_t gxs, 
     if (c) r += c[b * cs + s];
     out[b * os + s] = r;
   }
-}
-
-// grid of NS_VJP_SITES: x over the sites of a plane, y over the planes
-dim3 grid_for(int64_t planes, const Geo& g) {
-  return dim3((unsigned)std::min<int64_t>(bpk::ceil_div(g.hw, 256), 1 << 20),
-              (unsigned)std::min<int64_t>(planes, 65535));
 }
 
 #define NS_VJP_GEO_CHECK(B, nx, ny)                                                            \

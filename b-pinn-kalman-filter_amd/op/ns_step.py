@@ -6,7 +6,9 @@ only and out-of-place there.  Here `update_density`, `update_pressure`,
 `update_velocity(compat=False)` and `full_step(compat=False)` are also differentiable to
 first order (HIP gather adjoints, csrc/ns_step_vjp.hip) when grad mode is on and an input
 requires grad; without that they run exactly the forward launches.  A double backward
-raises.  `compat=True` stays forward-only and builds no graph.
+raises.  `compat=True` stays forward-only and builds no graph.  The linearized step is also
+available as functional calls at a given base state: `full_step_jvp` / `update_*_jvp` (the
+tangent-linear model, csrc/ns_step_jvp.hip) and `full_step_vjp` (its adjoint).
 
 `compat=True` (default, = reference behaviour) reproduces the unbind-stride quirk
 of update_velocity (op/ns_step.cpp:70): for batch >= 2 the u / v views of the
@@ -295,6 +297,131 @@ class _FullStep(torch.autograd.Function):
                                            ws.data_ptr(), B, nx, ny, ctx.dt, ctx.dx, st),
               "ns_step.full_step backward")
         return g_dens, (g_vel if need[1] else None), (g_pres if need[2] else None), None, None
+
+
+# ---- functional linear models at a given base state (csrc/ns_step_jvp.hip and
+# csrc/ns_step_vjp.hip), for callers that apply M or M^T many times at stored states (the
+# inner loop of incremental 4D-Var).  compat=False only; outputs carry no autograd graph.
+def _jvp_workspace(op, B, nx, ny, device):
+    nbytes = lib.bpk_ns_jvp_workspace_bytes(op, B, nx, ny)
+    return torch.empty(max(nbytes // 4, 1), device=device, dtype=torch.float32)
+
+
+def _linear_args(name, primals, others, kind):
+    """Check and detach the primals and their tangents / cotangents (`others`, aligned with
+    `primals`, None = zero); at least one of `others` is required."""
+    given = [t for t in others if t is not None]
+    _check(name, *primals, *given)
+    if not given:
+        raise RuntimeError(f"ns_step.{name}: at least one {kind} is required (all are None)")
+    for p, t in zip(primals, others):
+        if t is not None and t.shape != p.shape:
+            raise RuntimeError(f"ns_step.{name}: a {kind} must have the shape of its tensor, "
+                               f"got {list(t.shape)} for {list(p.shape)}")
+    return ([p.detach().contiguous() for p in primals],
+            [None if t is None else t.detach().contiguous() for t in others])
+
+
+def _same_geo(name, *ts):
+    geo = {(t.shape[0],) + tuple(t.shape[2:]) for t in ts}
+    if len(geo) != 1:
+        raise RuntimeError(f"ns_step.{name}: tensors disagree on [B, ., H, W]: "
+                           f"{[list(t.shape) for t in ts]}")
+
+
+def update_density_jvp(dens, vel, t_dens, t_vel, dt, dx):
+    """Tangent of update_density at (dens, vel): -> t_out.  A None tangent is zero."""
+    (dens, vel), (t_dens, t_vel) = _linear_args("update_density_jvp", (dens, vel),
+                                                (t_dens, t_vel), "tangent")
+    _same_geo("update_density_jvp", dens, vel)
+    B, nx, ny = _geo(dens)
+    out = torch.empty_like(dens)
+    ws = _jvp_workspace(0, B, nx, ny, dens.device)
+    check(lib.bpk_ns_update_density_jvp_f32(dens.data_ptr(), vel.data_ptr(), ptr(t_dens),
+                                            ptr(t_vel), out.data_ptr(), ws.data_ptr(), B, nx, ny,
+                                            float(dt), float(dx), stream_ptr(dens.device)),
+          "ns_step.update_density_jvp")
+    return out
+
+
+def update_velocity_jvp(vel, pres, t_vel, t_pres, dt, dx):
+    """Tangent of update_velocity(compat=False) at (vel, pres): -> t_out."""
+    (vel, pres), (t_vel, t_pres) = _linear_args("update_velocity_jvp", (vel, pres),
+                                                (t_vel, t_pres), "tangent")
+    _same_geo("update_velocity_jvp", vel, pres)
+    B, nx, ny = _geo(vel)
+    out = torch.empty_like(vel)
+    ws = _jvp_workspace(1, B, nx, ny, vel.device)
+    check(lib.bpk_ns_update_velocity_jvp_f32(vel.data_ptr(), pres.data_ptr(), ptr(t_vel),
+                                             ptr(t_pres), out.data_ptr(), ws.data_ptr(), B, nx,
+                                             ny, float(dt), float(dx), stream_ptr(vel.device)),
+          "ns_step.update_velocity_jvp")
+    return out
+
+
+def update_pressure_jvp(pres, vel, t_pres, t_vel, dt, dx):
+    """Tangent of update_pressure at (pres, vel): -> t_out (linear in pres, so only vel's
+    values enter)."""
+    (pres, vel), (t_pres, t_vel) = _linear_args("update_pressure_jvp", (pres, vel),
+                                                (t_pres, t_vel), "tangent")
+    _same_geo("update_pressure_jvp", pres, vel)
+    B, nx, ny = _geo(pres)
+    out = torch.empty_like(pres)
+    check(lib.bpk_ns_update_pressure_jvp_f32(vel.data_ptr(), ptr(t_pres), ptr(t_vel),
+                                             out.data_ptr(), B, nx, ny, float(dt), float(dx),
+                                             stream_ptr(pres.device)),
+          "ns_step.update_pressure_jvp")
+    return out
+
+
+def full_step_jvp(dens, vel, pres, t_dens, t_vel, t_pres, dt, dx, v1=None):
+    """Tangent-linear model of full_step(compat=False) at the base state (dens, vel, pres):
+    -> (t_d1, t_v1, t_p1).  A None tangent is zero; at least one is required.  v1: the base
+    step's velocity output when the caller has it; None runs the forward launch to get it."""
+    (dens, vel, pres), (t_dens, t_vel, t_pres) = _linear_args(
+        "full_step_jvp", (dens, vel, pres), (t_dens, t_vel, t_pres), "tangent")
+    _same_geo("full_step_jvp", dens, vel, pres)
+    if v1 is None:
+        v1 = _full_step(dens, vel, pres, dt, dx, False, None)[1]
+    else:
+        _check("full_step_jvp", v1)
+        if v1.shape != vel.shape:
+            raise RuntimeError(f"ns_step.full_step_jvp: v1 must have the shape of vel, got "
+                               f"{list(v1.shape)} for {list(vel.shape)}")
+        v1 = v1.detach().contiguous()
+    B, nx, ny = _geo(dens)
+    t_d1, t_v1, t_p1 = torch.empty_like(dens), torch.empty_like(vel), torch.empty_like(pres)
+    ws = _jvp_workspace(3, B, nx, ny, dens.device)
+    check(lib.bpk_ns_full_step_jvp_f32(dens.data_ptr(), vel.data_ptr(), pres.data_ptr(),
+                                       v1.data_ptr(), ptr(t_dens), ptr(t_vel), ptr(t_pres),
+                                       t_d1.data_ptr(), t_v1.data_ptr(), t_p1.data_ptr(),
+                                       ws.data_ptr(), B, nx, ny, float(dt), float(dx),
+                                       stream_ptr(dens.device)), "ns_step.full_step_jvp")
+    return t_d1, t_v1, t_p1
+
+
+def full_step_vjp(dens, vel, pres, v1, g_d1, g_v1, g_p1, dt, dx):
+    """Adjoint of full_step(compat=False) at the base state (dens, vel, pres) with velocity
+    output v1: cotangents of (d1, v1, p1) -> (g_dens, g_vel, g_pres).  A None cotangent is
+    zero; at least one is required.  The call `_FullStep.backward` makes when every input
+    needs its gradient, without a graph."""
+    (dens, vel, pres), (g_d1, g_v1, g_p1) = _linear_args(
+        "full_step_vjp", (dens, vel, pres), (g_d1, g_v1, g_p1), "cotangent")
+    _same_geo("full_step_vjp", dens, vel, pres)
+    _check("full_step_vjp", v1)
+    if v1.shape != vel.shape:
+        raise RuntimeError(f"ns_step.full_step_vjp: v1 must have the shape of vel, got "
+                           f"{list(v1.shape)} for {list(vel.shape)}")
+    v1 = v1.detach().contiguous()
+    B, nx, ny = _geo(dens)
+    g_dens, g_vel, g_pres = torch.empty_like(dens), torch.empty_like(vel), torch.empty_like(pres)
+    ws = _vjp_workspace(3, B, nx, ny, dens.device)
+    check(lib.bpk_ns_full_step_vjp_f32(dens.data_ptr(), vel.data_ptr(), pres.data_ptr(),
+                                       v1.data_ptr(), ptr(g_d1), ptr(g_v1), ptr(g_p1),
+                                       g_dens.data_ptr(), g_vel.data_ptr(), g_pres.data_ptr(),
+                                       ws.data_ptr(), B, nx, ny, float(dt), float(dx),
+                                       stream_ptr(dens.device)), "ns_step.full_step_vjp")
+    return g_dens, g_vel, g_pres
 
 
 # low-level kernels (one launch each), exposed for tests and custom pipelines

@@ -15,6 +15,10 @@ the patches as independent.
 Everything stays on the device: Adam is written out on tensors and the cost history is a
 device tensor, so `fit` never reads a value on the host.
 
+`IncrementalFourDVar` minimises the same cost the way variational assimilation is normally
+run: Gauss-Newton outer iterations around the current trajectory, conjugate gradients inside,
+each Hessian product one tangent-linear (csrc/ns_step_jvp.hip) and one adjoint sweep.
+
 No reference counterpart (the reference has no adjoint of its step).
 """
 from __future__ import annotations
@@ -141,3 +145,134 @@ class FourDVar:
             J, j_obs, j_b, traj = self._cost(x, obsv_seq, weights, background, background_weights)
         history.append(torch.stack([J, j_obs, j_b]))
         return FourDVarResult(state0=x, trajectory=traj, history=torch.stack(history))
+
+
+@dataclass
+class IncrementalResult(FourDVarResult):
+    # history: [outer + 1, 3] nonlinear (J, J_obs, J_b) at outer iterates 0 .. outer
+    cg_residuals: torch.Tensor = None  # [outer, inner + 1] |b - H dx| before / after each CG step
+
+
+class IncrementalFourDVar(FourDVar):
+    """Incremental (Gauss-Newton) 4D-Var: the same cost as `FourDVar`, minimised by an outer
+    loop that re-linearizes the model around the current trajectory and an inner conjugate-
+    gradient loop on the quadratic problem
+
+        H dx = b,   H = B^-1 + sum_t M_t^T W_t M_t,   b = B^-1 (x_b - x_k) + sum_t M_t^T W_t d_t
+
+    with d_t = y_t - x_t the innovations, M_t the tangent-linear model from x_0 to frame t and
+    M_t^T its adjoint.  One Hessian product is one tangent-linear sweep forward over the stored
+    states and one adjoint sweep back; no nonlinear forward runs inside the inner loop.
+
+    tangent_fn(d, v, p, v1, td, tv, tp) -> (td1, tv1, tp1): the step's tangent at the base
+    state (d, v, p) whose velocity output is v1; default `ns_step.full_step_jvp`.
+    adjoint_fn(d, v, p, v1, gd1, gv1, gp1) -> (gd, gv, gp): its adjoint; default
+    `ns_step.full_step_vjp`.  Both defaults take HIP tensors only; pass all three functions to
+    run the host logic on a restatement."""
+
+    def __init__(self, steps_per_frame=1, dt=simulator.dt, dx=simulator.dx, step_fn=None,
+                 tangent_fn=None, adjoint_fn=None):
+        super().__init__(steps_per_frame, dt, dx, step_fn)
+        if tangent_fn is None:
+            from op import ns_step
+
+            def tangent_fn(d, v, p, v1, td, tv, tp):
+                return ns_step.full_step_jvp(d, v, p, td, tv, tp, self.dt, self.dx, v1=v1)
+        if adjoint_fn is None:
+            from op import ns_step
+
+            def adjoint_fn(d, v, p, v1, gd1, gv1, gp1):
+                return ns_step.full_step_vjp(d, v, p, v1, gd1, gv1, gp1, self.dt, self.dx)
+        self.tangent_fn, self.adjoint_fn = tangent_fn, adjoint_fn
+
+    @staticmethod
+    def _split(x):
+        return x[:, 0:1].contiguous(), x[:, 1:3].contiguous(), x[:, 3:4].contiguous()
+
+    def _linearize(self, state0, T):
+        """Nonlinear rollout from state0 -> (frames [T, B, 4, H, W], the base state
+        (d, v, p, v1) of every sub-step in order)."""
+        if state0.ndim != 4 or state0.shape[1] != 4:
+            raise ValueError(f"FourDVar: state must be [B, 4, H, W], got {list(state0.shape)}")
+        f, v, p = self._split(state0)
+        states, frames = [], []
+        for _ in range(int(T)):
+            for _ in range(self.steps_per_frame):
+                f1, v1, p1 = self.step_fn(f, v, p)
+                states.append((f, v, p, v1))
+                f, v, p = f1.contiguous(), v1.contiguous(), p1.contiguous()
+            frames.append(torch.cat([f, v, p], dim=1))
+        return torch.stack(frames), states
+
+    def _tangent_sweep(self, states, dx0):
+        """M_t dx0 for every frame t -> [T, B, 4, H, W]."""
+        t = self._split(dx0)
+        frames = []
+        for i, base in enumerate(states):
+            t = self.tangent_fn(*base, *t)
+            if (i + 1) % self.steps_per_frame == 0:
+                frames.append(torch.cat(t, dim=1))
+        return torch.stack(frames)
+
+    def _adjoint_sweep(self, states, cots):
+        """sum_t M_t^T cots[t] -> [B, 4, H, W], accumulated backwards over the window."""
+        lam = torch.zeros_like(cots[0])
+        for i in range(len(states) - 1, -1, -1):
+            if (i + 1) % self.steps_per_frame == 0:
+                lam = lam + cots[(i + 1) // self.steps_per_frame - 1]
+            lam = torch.cat(self.adjoint_fn(*states[i], *self._split(lam)), dim=1)
+        return lam
+
+    def fit(self, obsv_seq, weights, background, background_weights, outer=3, inner=10):
+        """`outer` Gauss-Newton iterations from the background, each `inner` plain CG
+        iterations from dx = 0 (a fixed count: no host read decides anything).  alpha, beta
+        and the residual norms are 0-d device tensors; p.Hp = 0 (a converged system) yields a
+        zero update."""
+        if int(outer) < 1 or int(inner) < 1:
+            raise ValueError("IncrementalFourDVar: outer and inner must be >= 1")
+        weights = torch.as_tensor(weights, dtype=obsv_seq.dtype, device=obsv_seq.device)
+        bw = torch.as_tensor(background_weights, dtype=obsv_seq.dtype, device=obsv_seq.device)
+        T = obsv_seq.shape[0]
+        zero, one = obsv_seq.new_zeros(()), obsv_seq.new_ones(())
+
+        def nonlinear(x):
+            traj, states = self._linearize(x, T)
+            j_obs = 0.5 * (weights * (traj - obsv_seq) ** 2).sum()
+            j_b = 0.5 * (bw * (x - background) ** 2).sum()
+            return traj, states, torch.stack([j_obs + j_b, j_obs, j_b])
+
+        def ratio(num, den):
+            ok = den > 0
+            return torch.where(ok, num / torch.where(ok, den, one), zero)
+
+        with torch.no_grad():
+            x = background.detach().clone()
+            history, residuals = [], []
+            for _ in range(int(outer)):
+                traj, states, cost = nonlinear(x)
+                history.append(cost)
+
+                def hess(vec):
+                    return bw * vec + self._adjoint_sweep(
+                        states, weights * self._tangent_sweep(states, vec))
+
+                b = bw * (background - x) + self._adjoint_sweep(
+                    states, (weights * (obsv_seq - traj)).expand_as(traj))
+                dx0, r, p = torch.zeros_like(x), b, b
+                rs = (r * r).sum()
+                res = [rs.sqrt()]
+                for _ in range(int(inner)):
+                    hp = hess(p)
+                    alpha = ratio(rs, (p * hp).sum())
+                    dx0 = dx0 + alpha * p
+                    r = r - alpha * hp
+                    rs_new = (r * r).sum()
+                    p = r + ratio(rs_new, rs) * p
+                    rs = rs_new
+                    res.append(rs.sqrt())
+                residuals.append(torch.stack(res))
+                x = x + dx0
+            traj, _, cost = nonlinear(x)
+            history.append(cost)
+        return IncrementalResult(state0=x, trajectory=traj, history=torch.stack(history),
+                                 cg_residuals=torch.stack(residuals))

@@ -262,6 +262,36 @@ int bpk_ns_full_step_vjp_f32(const float* dens, const float* vel, const float* p
                              void* workspace, int B, int nx, int ny, float dt, float dx,
                              void* stream);
 
+/* Jacobian-vector products (the tangent-linear model) of the step with compat = 0
+ * (csrc/ns_step_jvp.hip): given tangents of the inputs at a base state, the tangents of the
+ * outputs.  Pure gathers in plain float32, no atomics, bit-reproducible; sgn(u), sgn(v) and
+ * the upwind indices are constants of the derivative, taken from the base state exactly as
+ * the forward and the VJP take them.  Layout as the VJP's: velocity tensors and their
+ * tangents are 2B planes, everything else B contiguous planes; nx, ny >= 2.
+ * Scratch: bpk_ns_jvp_workspace_bytes(op, B, nx, ny) bytes (op as the VJP's: 0 =
+ * update_density, 1 = update_velocity, 2 = update_pressure (none), 3 = full_step).
+ *
+ * An input tangent that is NULL is zero; at least one must be given.  t_out (and the three
+ * outputs of full_step_jvp) are required and must not alias an input.
+ * update_*_jvp: the tangent of the op of that name, in its argument order (update_pressure
+ *   takes pres first: t_pres, then t_vel; pres itself does not enter its derivative).
+ * full_step_jvp: vel1 = the base step's velocity output, as full_step_vjp takes it. */
+int64_t bpk_ns_jvp_workspace_bytes(int op, int B, int nx, int ny);
+int bpk_ns_update_density_jvp_f32(const float* dens, const float* vel, const float* t_dens,
+                                  const float* t_vel, float* t_out, void* workspace, int B,
+                                  int nx, int ny, float dt, float dx, void* stream);
+int bpk_ns_update_velocity_jvp_f32(const float* vel, const float* pres, const float* t_vel,
+                                   const float* t_pres, float* t_out, void* workspace, int B,
+                                   int nx, int ny, float dt, float dx, void* stream);
+int bpk_ns_update_pressure_jvp_f32(const float* vel, const float* t_pres, const float* t_vel,
+                                   float* t_out, int B, int nx, int ny, float dt, float dx,
+                                   void* stream);
+int bpk_ns_full_step_jvp_f32(const float* dens, const float* vel, const float* pres,
+                             const float* vel1, const float* t_dens, const float* t_vel,
+                             const float* t_pres, float* t_dens1, float* t_vel1, float* t_pres1,
+                             void* workspace, int B, int nx, int ny, float dt, float dx,
+                             void* stream);
+
 /* ------------------------------------------------------------------------- *
  * GroupNorm (+ optional fused per-(n,c) bias before the norm and SiLU after).
  * The build's fusion of nn.GroupNorm + act + `h += Dense(temb)[:, :, None, None]`
