@@ -1,21 +1,17 @@
 // Derivative pieces of one CIP site, shared by the adjoint (ns_step_vjp.hip) and the
 // tangent-linear model (ns_step_jvp.hip) of the Navier-Stokes step: the weights
-// d out / d (gathered value), the local derivatives d out / d (X, Y), the mirror clamp, the
-// site loop and its grid.  One copy of the formulas, so a site takes the same branch and the
-// same weights in both directions.
+// d out / d (gathered value), the local derivatives d out / d (X, Y), the site loop and its
+// grid.  One copy of the formulas, so a site takes the same weights in both directions.  On
+// top of ns_common.h (Geo, clampx, sgn, CipVals / cip_gather, the argument checks), which the
+// forward shares.
 //
 // Plain float32 with FMA contraction; none of the forward's exact-division machinery.
 #pragma once
 #include <algorithm>
 
-#include "bpk_common.h"
+#include "ns_common.h"
 
 namespace {
-
-struct Geo {
-  int nx, ny;
-  int64_t hw;
-};
 
 struct VjpConst {
   float dt, dx, r1, r2, r3;  // 1/dx, 1/dx^2, 1/dx^3
@@ -25,10 +21,6 @@ struct VjpConst {
     r3 = r2 * r1;
   }
 };
-
-__device__ inline int clampx(int x, int n) { return x < 0 ? -x : (x > n - 1 ? 2 * n - 2 - x : x); }
-
-__device__ inline int sgn(float v) { return v < 0.0f ? -1 : (v > 0.0f ? 1 : 0); }
 
 // One thread per site, x fastest: blockIdx.y walks the planes and blockIdx.x the sites of a
 // plane, so no thread pays a 64-bit division to find its plane.  Closes with one brace.
@@ -43,19 +35,9 @@ inline dim3 grid_for(int64_t planes, const Geo& g) {
               (unsigned)std::min<int64_t>(planes, 65535));
 }
 
-// d out / d (gathered value) of one CIP site, from the site's velocity alone
-struct CipW {
-  float f_c, f_xm, f_ym, f_xy;
-  float fx_c, fx_xm, fx_ym;
-  float fy_c, fy_xm, fy_ym;
-};
-
-// the ten gathered values of one CIP site (CipIn of ns_step.hip)
-struct CipVals {
-  float f_c, f_xm, f_ym, f_xy;
-  float fx_c, fx_xm, fx_ym;
-  float fy_c, fy_xm, fy_ym;
-};
+// d out / d (gathered value) of one CIP site, from the site's velocity alone: one weight per
+// gathered value
+using CipW = CipVals;
 
 // out = a X^3 + c X^2 Y + e X^2 + g X Y + fx_c X + b Y^3 + d X Y^2 + f Y^2 + fy_c Y + f_c
 // with (ns_step.hip cip_site_fast; 1/s = s for s = +-1)
@@ -129,20 +111,6 @@ __device__ inline void cip_dxy_vals(const CipVals& q, float u, float v, int sxi,
   const float X = -u * k.dt, Y = -v * k.dt;
   *dX = (3.0f * a * X + 2.0f * cc * Y + 2.0f * e) * X + (gg + d * Y) * Y + fx_c;
   *dY = (3.0f * b * Y + 2.0f * d * X + 2.0f * ff) * Y + (gg + cc * X) * X + fy_c;
-}
-
-// the ten values of site (x, y) with upwind indices (xm, ym) from a field and its stored
-// stencil gradient
-__device__ inline CipVals cip_gather(const float* __restrict__ f, const float* __restrict__ fx,
-                                     const float* __restrict__ fy, int x, int y, int xm, int ym,
-                                     const Geo& g) {
-  const int64_t c = (int64_t)y * g.nx + x, cxm = (int64_t)y * g.nx + xm,
-                cym = (int64_t)ym * g.nx + x, cxy = (int64_t)ym * g.nx + xm;
-  CipVals q;
-  q.f_c = f[c], q.f_xm = f[cxm], q.f_ym = f[cym], q.f_xy = f[cxy];
-  q.fx_c = fx[c], q.fx_xm = fx[cxm], q.fx_ym = fx[cym];
-  q.fy_c = fy[c], q.fy_xm = fy[cxm], q.fy_ym = fy[cym];
-  return q;
 }
 
 __device__ inline void cip_dxy(const float* __restrict__ f, const float* __restrict__ fx,

@@ -17,33 +17,16 @@
 //  * the whole simulator step (velocity -> pressure -> density) runs as two
 //    fused kernels that recompute the intermediate fields from cached inputs
 //    instead of 7+ launches that round-trip every intermediate through HBM.
-#include "bpk_common.h"
+//
+// Geo, clampx, sgn, CipVals / cip_gather, NS_PRES_NEIGHBOURS, NS_GEO_CHECK and
+// velocity_stage_base are shared with the adjoint and the tangent: ns_common.h.
+#include "ns_common.h"
 
+// after the includes: everything below, and nothing in a header, is compiled without FMA
+// contraction, so all floating-point arithmetic of the forward stays in this file
 #pragma clang fp contract(off)
 
 namespace {
-
-struct Geo {
-  int nx, ny;
-  int64_t hw;
-};
-
-__device__ inline int clampx(int x, int n) { return x < 0 ? -x : (x > n - 1 ? 2 * n - 2 - x : x); }
-
-template <typename T>
-__device__ inline int sgn(T v) {
-  if (v < 0.0) return -1;
-  if (v > 0.0) return 1;
-  return 0;
-}
-
-// CIP advection of one site (op/ns_step_kernel.cu:115-158), operands passed as
-// plane pointers so callers can supply stored or recomputed fields.
-struct CipIn {
-  float f_c, f_ym, f_xm, f_xmym;  // f(x,y) f(x,ym) f(xm,y) f(xm,ym)
-  float fx_c, fx_xm, fx_ym;       // fx(x,y) fx(xm,y) fx(x,ym)
-  float fy_c, fy_xm, fy_ym;       // fy(x,y) fy(xm,y) fy(x,ym)
-};
 
 // Correctly rounded division without the IEEE divide sequence.  For b != 0 with
 // r = RN(1/b) and q = RN(a*r) (within 1 ulp of a/b), the residual a - b*q is exact
@@ -118,11 +101,11 @@ __device__ inline double div_sd3(double d, int s, const NsConst& k) {
 
 // cip_site (op/ns_step_kernel.cu:115-158) with the cheap exact divisions; every
 // expression keeps the reference's float/double types and operation order.
-__device__ inline float cip_site_fast(const CipIn& q, float u, float v, const NsConst& k) {
+__device__ inline float cip_site_fast(const CipVals& q, float u, float v, const NsConst& k) {
   const int x_s = sgn(u);
   const int y_s = sgn(v);
   const float dx = k.dx;
-  float tmp1 = q.f_c - q.f_ym - q.f_xm + q.f_xmym;
+  float tmp1 = q.f_c - q.f_ym - q.f_xm + q.f_xy;
   float tmp2 = q.f_xm - q.f_c;
   float tmp3 = q.f_ym - q.f_c;
   float a = (float)div_sd3((double)(x_s * (q.fx_xm + q.fx_c) * dx) - 2.0 * (-tmp2), x_s, k);
@@ -162,7 +145,7 @@ __device__ inline float ddy(const float* f, int x, int y, const Geo& g, const Ns
 }
 
 // pressure update of one site (op/ns_step_kernel.cu:205-234):
-// sub_x = V(xu) - V(xd), sub_y = V(yu) - V(yd)
+// sub_x = V(xu) - V(xd), sub_y = V(yu) - V(yd) over the planes p, u, v of one sample
 __device__ inline float pres_site(float p_xd, float p_xu, float p_yd, float p_yu, float u_xu,
                                   float u_xd, float v_xu, float v_xd, float u_yu, float u_yd,
                                   float v_yu, float v_yd, float dt, float dx, float r8dt,
@@ -193,24 +176,6 @@ __global__ __launch_bounds__(256) void k_gradient(const float* __restrict__ f, i
   }
 }
 
-__device__ inline CipIn gather_cip(const float* fp, const float* fxp, const float* fyp, int x,
-                                   int y, int xm, int ym, int nx) {
-  CipIn q;
-  const int64_t c = (int64_t)y * nx + x, cxm = (int64_t)y * nx + xm, cym = (int64_t)ym * nx + x,
-                cxy = (int64_t)ym * nx + xm;
-  q.f_c = fp[c];
-  q.f_ym = fp[cym];
-  q.f_xm = fp[cxm];
-  q.f_xmym = fp[cxy];
-  q.fx_c = fxp[c];
-  q.fx_xm = fxp[cxm];
-  q.fx_ym = fxp[cym];
-  q.fy_c = fyp[c];
-  q.fy_xm = fyp[cxm];
-  q.fy_ym = fyp[cym];
-  return q;
-}
-
 // out[b] (plane stride ostride) = CIP(f[b] with stride fstride, fx/fy contiguous, vel[b])
 __global__ __launch_bounds__(256) void k_cip(const float* __restrict__ f, int64_t fstride,
                                              const float* __restrict__ fx,
@@ -229,7 +194,7 @@ __global__ __launch_bounds__(256) void k_cip(const float* __restrict__ f, int64_
     const float v = vel[(2 * b + 1) * g.hw + s];
     const int xm = clampx(x - sgn(u), g.nx);
     const int ym = clampx(y - sgn(v), g.ny);
-    const CipIn q = gather_cip(f + b * fstride, fx + b * g.hw, fy + b * g.hw, x, y, xm, ym, g.nx);
+    const CipVals q = cip_gather(f + b * fstride, fx + b * g.hw, fy + b * g.hw, x, y, xm, ym, g);
     out[b * ostride + s] = cip_site_fast(q, u, v, c);
   }
 }
@@ -276,13 +241,10 @@ __global__ __launch_bounds__(256) void k_pres_update(const float* __restrict__ p
     const int64_t b = i / g.hw;
     const int s = (int)(i - b * g.hw);
     const int y = s / g.nx, x = s - y * g.nx;
-    const int xu = clampx(x + 1, g.nx), xd = clampx(x - 1, g.nx);
-    const int yu = clampx(y + 1, g.ny), yd = clampx(y - 1, g.ny);
     const float* p = pres + b * g.hw;
     const float* u = vel + (2 * b) * g.hw;
     const float* v = vel + (2 * b + 1) * g.hw;
-    const int64_t ixu = (int64_t)y * g.nx + xu, ixd = (int64_t)y * g.nx + xd,
-                  iyu = (int64_t)yu * g.nx + x, iyd = (int64_t)yd * g.nx + x;
+    NS_PRES_NEIGHBOURS(x, y, g);
     pres_n[i] = pres_site(p[ixd], p[ixu], p[iyd], p[iyu], u[ixu], u[ixd], v[ixu], v[ixd], u[iyu],
                           u[iyd], v[iyu], v[iyd], dt, dx, r8dt, ok8);
   }
@@ -305,17 +267,7 @@ constexpr int kGW = kTX + 2, kGH = kTY + 2;  // gradient tile (+1 halo)
 __device__ inline float veln_at(const float* __restrict__ vel, const float* __restrict__ pres,
                                 int64_t k, int x, int y, const Geo& g, const NsConst& c) {
   const float* p = pres + (k >> 1) * g.hw;
-  float grad;
-  if (k & 1) {
-    if (y == 0) grad = c.over_dx(p[(int64_t)(y + 1) * g.nx + x] - p[(int64_t)y * g.nx + x]);
-    else if (y == g.ny - 1) grad = c.over_dx(p[(int64_t)y * g.nx + x] - p[(int64_t)(y - 1) * g.nx + x]);
-    else grad = c.over_2dx(p[(int64_t)(y + 1) * g.nx + x] - p[(int64_t)(y - 1) * g.nx + x]);
-  } else {
-    const float* r = p + (int64_t)y * g.nx;
-    if (x == 0) grad = c.over_dx(r[x + 1] - r[x]);
-    else if (x == g.nx - 1) grad = c.over_dx(r[x] - r[x - 1]);
-    else grad = c.over_2dx(r[x + 1] - r[x - 1]);
-  }
+  const float grad = (k & 1) ? ddy(p, x, y, g, c) : ddx(p, x, y, g, c);
   return vel[k * g.hw + (int64_t)y * g.nx + x] - grad * c.dt;
 }
 
@@ -385,11 +337,11 @@ __global__ __launch_bounds__(256) void k_fused_velocity_lds(const float* __restr
         const int64_t s = (int64_t)y * g.nx + x;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
-          CipIn q;
+          CipVals q;
           q.f_c = sF[pl][fyc][fxc];
           q.f_ym = sF[pl][fym][fxc];
           q.f_xm = sF[pl][fyc][fxm];
-          q.f_xmym = sF[pl][fym][fxm];
+          q.f_xy = sF[pl][fym][fxm];
           q.fx_c = sFx[pl][gyc][gxc];
           q.fx_xm = sFx[pl][gyc][gxm];
           q.fx_ym = sFx[pl][gym][gxc];
@@ -425,10 +377,7 @@ __global__ __launch_bounds__(256) void k_fused_pres_dens(const float* __restrict
     const float* u = vel1 + (2 * b) * g.hw;
     const float* v = vel1 + (2 * b + 1) * g.hw;
     {
-      const int xu = clampx(x + 1, g.nx), xd = clampx(x - 1, g.nx);
-      const int yu = clampx(y + 1, g.ny), yd = clampx(y - 1, g.ny);
-      const int64_t ixu = (int64_t)y * g.nx + xu, ixd = (int64_t)y * g.nx + xd,
-                    iyu = (int64_t)yu * g.nx + x, iyd = (int64_t)yd * g.nx + x;
+      NS_PRES_NEIGHBOURS(x, y, g);
       pres_out[i] = pres_site(p[ixd], p[ixu], p[iyd], p[iyu], u[ixu], u[ixd], v[ixu], v[ixd],
                               u[iyu], u[iyd], v[iyu], v[iyd], dt, dx, r8dt, ok8);
     }
@@ -436,11 +385,11 @@ __global__ __launch_bounds__(256) void k_fused_pres_dens(const float* __restrict
     const int xm = clampx(x - sgn(uc), g.nx);
     const int ym = clampx(y - sgn(vc), g.ny);
     const float* f = dens + b * g.hw;
-    CipIn q;
+    CipVals q;
     q.f_c = f[s];
     q.f_ym = f[(int64_t)ym * g.nx + x];
     q.f_xm = f[(int64_t)y * g.nx + xm];
-    q.f_xmym = f[(int64_t)ym * g.nx + xm];
+    q.f_xy = f[(int64_t)ym * g.nx + xm];
     q.fx_c = ddx(f, x, y, g, c);
     q.fx_xm = ddx(f, xm, y, g, c);
     q.fx_ym = ddx(f, x, ym, g, c);
@@ -452,7 +401,8 @@ __global__ __launch_bounds__(256) void k_fused_pres_dens(const float* __restrict
 }
 
 // out[x] = sum_j coef(j, x) g[j] for the 1-D stencil D of diff_x: interior rows j give
-// +-1/(2dx) to x = j+-1, border rows give +-1/dx (one-sided differences)
+// +-1/(2dx) to x = j+-1, border rows give +-1/dx (one-sided differences).
+// Not k_grad_vjp of ns_step_vjp.hip: contraction off here, the PINN fixtures rest on these bits.
 __device__ inline float adj1d(const float* g, int64_t stride, int x, int n, float dx) {
   float acc = 0.f;
   auto coef = [&](int j, int xx) -> float {  // coefficient of f[xx] in (D f)[j]
@@ -485,80 +435,62 @@ unsigned grid_for(int64_t total) {
   return (unsigned)std::min<int64_t>(bpk::ceil_div(total, 256), 256 * 64);
 }
 
-#define NS_GEO_CHECK(B, nx, ny)                                                            \
-  BPK_REQUIRE((B) >= 0 && (nx) >= 2 && (ny) >= 2, "ns_step: need B >= 0 and planes >= 2x2 " \
-                                                  "(got B=%d nx=%d ny=%d)",               \
-              (B), (nx), (ny))
+// A one-kernel entry: the geometry check, nothing to do for B == 0, one launch over the sites
+// of B planes, the launch check.  args: the kernel's own, in its order.
+template <typename... P, typename... A>
+int launch_sites(const char* what, void (*kernel)(P...), const Geo& g, int B, void* stream,
+                 A... args) {
+  NS_GEO_CHECK("ns_step", B, g.nx, g.ny);
+  if (B == 0) return BPK_OK;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(B * g.hw)), dim3(256), 0, bpk::as_stream(stream),
+                     args...);
+  BPK_LAUNCH_CHECK(what);
+  return BPK_OK;
+}
 
 }  // namespace
 
 extern "C" int bpk_ns_gradient_f32(const float* f, int64_t f_plane_stride, float* fx, float* fy,
                                    int B, int nx, int ny, float dx, void* stream) {
-  NS_GEO_CHECK(B, nx, ny);
   const Geo g{nx, ny, (int64_t)nx * ny};
-  if (B == 0) return BPK_OK;
-  hipLaunchKernelGGL(k_gradient, dim3(grid_for(B * g.hw)), dim3(256), 0, bpk::as_stream(stream), f,
-                     f_plane_stride, fx, fy, B, g, dx);
-  BPK_LAUNCH_CHECK("ns_gradient");
-  return BPK_OK;
+  return launch_sites("ns_gradient", k_gradient, g, B, stream, f, f_plane_stride, fx, fy, B, g, dx);
 }
 
 extern "C" int bpk_ns_gradient_adjoint_f32(const float* gx, const float* gy, float* out, int B,
                                            int nx, int ny, float dx, void* stream) {
-  NS_GEO_CHECK(B, nx, ny);
   const Geo g{nx, ny, (int64_t)nx * ny};
-  if (B == 0) return BPK_OK;
-  hipLaunchKernelGGL(k_gradient_adjoint, dim3(grid_for(B * g.hw)), dim3(256), 0,
-                     bpk::as_stream(stream), gx, gy, out, B, g, dx);
-  BPK_LAUNCH_CHECK("ns_gradient_adjoint");
-  return BPK_OK;
+  return launch_sites("ns_gradient_adjoint", k_gradient_adjoint, g, B, stream, gx, gy, out, B, g,
+                      dx);
 }
 
 extern "C" int bpk_ns_cip_advect_f32(const float* f, int64_t f_plane_stride, const float* fx,
                                      const float* fy, const float* vel, float* out, int B, int nx,
                                      int ny, float dt, float dx, void* stream) {
-  NS_GEO_CHECK(B, nx, ny);
   const Geo g{nx, ny, (int64_t)nx * ny};
-  if (B == 0) return BPK_OK;
-  hipLaunchKernelGGL(k_cip, dim3(grid_for(B * g.hw)), dim3(256), 0, bpk::as_stream(stream), f,
-                     f_plane_stride, fx, fy, vel, out, g.hw, B, g, dt, dx);
-  BPK_LAUNCH_CHECK("ns_cip_advect");
-  return BPK_OK;
+  return launch_sites("ns_cip_advect", k_cip, g, B, stream, f, f_plane_stride, fx, fy, vel, out,
+                      g.hw, B, g, dt, dx);
 }
 
 extern "C" int bpk_ns_advect_f32(const float* f, int64_t f_plane_stride, const float* fx,
                                  const float* fy, const float* vel, float* out, int B, int nx,
                                  int ny, float dt, void* stream) {
-  NS_GEO_CHECK(B, nx, ny);
   const Geo g{nx, ny, (int64_t)nx * ny};
-  if (B == 0) return BPK_OK;
-  hipLaunchKernelGGL(k_advect, dim3(grid_for(B * g.hw)), dim3(256), 0, bpk::as_stream(stream), f,
-                     f_plane_stride, fx, fy, vel, out, B, g, dt);
-  BPK_LAUNCH_CHECK("ns_advect");
-  return BPK_OK;
+  return launch_sites("ns_advect", k_advect, g, B, stream, f, f_plane_stride, fx, fy, vel, out, B,
+                      g, dt);
 }
 
 extern "C" int bpk_ns_vel_update_f32(const float* vel, const float* px, const float* py,
                                      float* vel_n, int B, int nx, int ny, float dt,
                                      void* stream) {
-  NS_GEO_CHECK(B, nx, ny);
   const Geo g{nx, ny, (int64_t)nx * ny};
-  if (B == 0) return BPK_OK;
-  hipLaunchKernelGGL(k_vel_update, dim3(grid_for(B * g.hw)), dim3(256), 0, bpk::as_stream(stream),
-                     vel, px, py, vel_n, B, g, dt);
-  BPK_LAUNCH_CHECK("ns_vel_update");
-  return BPK_OK;
+  return launch_sites("ns_vel_update", k_vel_update, g, B, stream, vel, px, py, vel_n, B, g, dt);
 }
 
 extern "C" int bpk_ns_pres_update_f32(const float* pres, const float* vel, float* pres_n, int B,
                                       int nx, int ny, float dt, float dx, void* stream) {
-  NS_GEO_CHECK(B, nx, ny);
   const Geo g{nx, ny, (int64_t)nx * ny};
-  if (B == 0) return BPK_OK;
-  hipLaunchKernelGGL(k_pres_update, dim3(grid_for(B * g.hw)), dim3(256), 0,
-                     bpk::as_stream(stream), pres, vel, pres_n, B, g, dt, dx);
-  BPK_LAUNCH_CHECK("ns_pres_update");
-  return BPK_OK;
+  return launch_sites("ns_pres_update", k_pres_update, g, B, stream, pres, vel, pres_n, B, g, dt,
+                      dx);
 }
 
 extern "C" int64_t bpk_ns_workspace_bytes(int op, int B, int nx, int ny) {
@@ -574,7 +506,7 @@ extern "C" int64_t bpk_ns_workspace_bytes(int op, int B, int nx, int ny) {
 extern "C" int bpk_ns_update_density_f32(const float* dens, const float* vel, float* out,
                                          void* workspace, int B, int nx, int ny, float dt,
                                          float dx, void* stream) {
-  NS_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(workspace, "ns_update_density: workspace required");
   const int64_t hw = (int64_t)nx * ny;
@@ -588,37 +520,26 @@ extern "C" int bpk_ns_update_density_f32(const float* dens, const float* vel, fl
 extern "C" int bpk_ns_update_velocity_f32(const float* vel, const float* pres, float* out,
                                           void* workspace, int B, int nx, int ny, float dt,
                                           float dx, int compat, void* stream) {
-  NS_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(workspace, "ns_update_velocity: workspace required");
   const Geo g{nx, ny, (int64_t)nx * ny};
   const int64_t hw = g.hw;
-  float* px = static_cast<float*>(workspace);
-  float* py = px + B * hw;
-  float* vel_n = py + B * hw;
-  float* dudx = vel_n + 2 * B * hw;
-  float* dudy = dudx + B * hw;
-  float* dvdx = dudy + B * hw;
-  float* dvdy = dvdx + B * hw;
-  int rc = bpk_ns_gradient_f32(pres, hw, px, py, B, nx, ny, dx, stream);
-  if (rc) return rc;
-  rc = bpk_ns_vel_update_f32(vel, px, py, vel_n, B, nx, ny, dt, stream);
+  float *ws = static_cast<float*>(workspace), *vel_n;
+  int rc = velocity_stage_base(vel, pres, ws, &vel_n, B, g, dt, dx, stream);
   if (rc) return rc;
   // op/ns_step.cpp:70 -- unbind(vel_n, 1) views read with batch stride hw (compat)
   const int64_t fstride = compat ? hw : 2 * hw;
-  const float* ufield = vel_n;
-  const float* vfield = vel_n + hw;
-  hipStream_t st = bpk::as_stream(stream);
-  rc = bpk_ns_gradient_f32(ufield, fstride, dudx, dudy, B, nx, ny, dx, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_cip, dim3(grid_for(B * hw)), dim3(256), 0, st, ufield, fstride, dudx, dudy,
-                     vel_n, out, 2 * hw, B, g, dt, dx);
-  BPK_LAUNCH_CHECK("ns_update_velocity(u)");
-  rc = bpk_ns_gradient_f32(vfield, fstride, dvdx, dvdy, B, nx, ny, dx, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_cip, dim3(grid_for(B * hw)), dim3(256), 0, st, vfield, fstride, dvdx, dvdy,
-                     vel_n, out + hw, 2 * hw, B, g, dt, dx);
-  BPK_LAUNCH_CHECK("ns_update_velocity(v)");
+  for (int j = 0; j < 2; ++j) {  // the u field, then the v field
+    const float* field = vel_n + j * hw;
+    float* dfx = ws + (4 + 2 * j) * B * hw;  // its stencil gradient, B planes each
+    float* dfy = dfx + B * hw;
+    rc = bpk_ns_gradient_f32(field, fstride, dfx, dfy, B, nx, ny, dx, stream);
+    if (rc) return rc;
+    rc = launch_sites(j ? "ns_update_velocity(v)" : "ns_update_velocity(u)", k_cip, g, B, stream,
+                      field, fstride, dfx, dfy, vel_n, out + j * hw, 2 * hw, B, g, dt, dx);
+    if (rc) return rc;
+  }
   return BPK_OK;
 }
 
@@ -639,7 +560,7 @@ extern "C" int bpk_ns_full_step_f32(const float* dens, const float* vel, const f
                                     void* workspace, int B, int nx, int ny, float dt, float dx,
                                     int compat, void* stream) {
   (void)workspace;
-  NS_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step", B, nx, ny);
   if (B == 0) return BPK_OK;
   const Geo g{nx, ny, (int64_t)nx * ny};
   hipStream_t st = bpk::as_stream(stream);

@@ -35,8 +35,10 @@
 // Plain float32 with FMA contraction; none of the forward's exact-division machinery.
 // A velocity component exactly 0 makes the forward non-finite (a reference property); the
 // tangent there is unspecified, but sgn = 0 gives xm = x, so every index stays in bounds.
-#include <climits>
-
+//
+// ns_common.h (shared with the forward): Geo, clampx, sgn, CipVals, cip_gather,
+// NS_PRES_NEIGHBOURS, NS_GEO_CHECK, NS_HIP_OK, velocity_stage_base.  ns_cip_deriv.h (shared with
+// the adjoint): VjpConst, NS_VJP_SITES, grid_for, cip_weights, cip_dot, cip_dxy_vals.
 #include "ns_cip_deriv.h"
 
 namespace {
@@ -170,10 +172,7 @@ __global__ __launch_bounds__(256) void k_pres_dens_jvp(const float* __restrict__
     const float* tu = tvel1 ? tvel1 + (2 * b) * g.hw : nullptr;
     const float* tv = tvel1 ? tvel1 + (2 * b + 1) * g.hw : nullptr;
     if (t_p1) {
-      const int xu = clampx(x + 1, g.nx), xd = clampx(x - 1, g.nx);
-      const int yu = clampx(y + 1, g.ny), yd = clampx(y - 1, g.ny);
-      const int64_t ixu = (int64_t)y * g.nx + xu, ixd = (int64_t)y * g.nx + xd,
-                    iyu = (int64_t)yu * g.nx + x, iyd = (int64_t)yd * g.nx + x;
+      NS_PRES_NEIGHBOURS(x, y, g);
       float r = 0.f;
       if (tpres) {
         const float* tp = tpres + b * g.hw;
@@ -213,16 +212,6 @@ __global__ __launch_bounds__(256) void k_pres_dens_jvp(const float* __restrict__
   }
 }
 
-#define NS_JVP_GEO_CHECK(B, nx, ny)                                                            \
-  do {                                                                                         \
-    BPK_REQUIRE((B) >= 0 && (nx) >= 2 && (ny) >= 2, "ns_step jvp: need B >= 0 and planes >= "   \
-                                                    "2x2 (got B=%d nx=%d ny=%d)",              \
-                (B), (nx), (ny));                                                              \
-    BPK_REQUIRE((int64_t)(nx) * (ny) <= INT_MAX, "ns_step jvp: planes of at most 2^31 - 1 "     \
-                                                 "sites (got nx=%d ny=%d)",                    \
-                (nx), (ny));                                                                   \
-  } while (0)
-
 int launch_pres_dens_jvp(const float* dens, const float* vel1, const float* tdens,
                          const float* tvel1, const float* tpres, float* t_d1, float* t_p1, int B,
                          const Geo& g, float dt, float dx, hipStream_t st, const char* what) {
@@ -239,15 +228,9 @@ int velocity_stage_jvp(const float* vel, const float* pres, const float* t_vel,
                        float dt, float dx, void* stream) {
   const int64_t hw = g.hw, P = (int64_t)B * hw;
   hipStream_t st = bpk::as_stream(stream);
-  float* px = ws;
-  float* py = ws + P;
-  float* vel_n = ws + 2 * P;   // 2B planes
+  float* vel_n;                // first 4B planes: velocity_stage_base
   float* tvel_n = ws + 4 * P;  // 2B planes: tangent of vel_n
-  // un, vn recomputed with the forward's own kernels (the same bits, hence the same signs, as
-  // the fused forward and the adjoint)
-  int rc = bpk_ns_gradient_f32(pres, hw, px, py, B, g.nx, g.ny, dx, stream);
-  if (rc) return rc;
-  rc = bpk_ns_vel_update_f32(vel, px, py, vel_n, B, g.nx, g.ny, dt, stream);
+  int rc = velocity_stage_base(vel, pres, ws, &vel_n, B, g, dt, dx, stream);
   if (rc) return rc;
   hipLaunchKernelGGL(k_veln_jvp, grid_for(B, g), dim3(256), 0, st, t_vel, t_pres, tvel_n, B, g,
                      dt, dx);
@@ -284,7 +267,7 @@ extern "C" int bpk_ns_update_density_jvp_f32(const float* dens, const float* vel
                                              const float* t_dens, const float* t_vel,
                                              float* t_out, void* workspace, int B, int nx, int ny,
                                              float dt, float dx, void* stream) {
-  NS_JVP_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step jvp", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(dens && vel && t_out, "ns_update_density_jvp: dens, vel and t_out required");
   BPK_REQUIRE(t_dens || t_vel, "ns_update_density_jvp: no tangent given");
@@ -323,7 +306,7 @@ extern "C" int bpk_ns_update_velocity_jvp_f32(const float* vel, const float* pre
                                               const float* t_vel, const float* t_pres,
                                               float* t_out, void* workspace, int B, int nx,
                                               int ny, float dt, float dx, void* stream) {
-  NS_JVP_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step jvp", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(vel && pres && t_out, "ns_update_velocity_jvp: vel, pres and t_out required");
   BPK_REQUIRE(t_vel || t_pres, "ns_update_velocity_jvp: no tangent given");
@@ -336,7 +319,7 @@ extern "C" int bpk_ns_update_velocity_jvp_f32(const float* vel, const float* pre
 extern "C" int bpk_ns_update_pressure_jvp_f32(const float* vel, const float* t_pres,
                                               const float* t_vel, float* t_out, int B, int nx,
                                               int ny, float dt, float dx, void* stream) {
-  NS_JVP_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step jvp", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(vel && t_out, "ns_update_pressure_jvp: vel and t_out required");
   BPK_REQUIRE(t_pres || t_vel, "ns_update_pressure_jvp: no tangent given");
@@ -350,7 +333,7 @@ extern "C" int bpk_ns_full_step_jvp_f32(const float* dens, const float* vel, con
                                         const float* t_vel, const float* t_pres, float* t_dens1,
                                         float* t_vel1, float* t_pres1, void* workspace, int B,
                                         int nx, int ny, float dt, float dx, void* stream) {
-  NS_JVP_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step jvp", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(dens && vel && pres && vel1, "ns_full_step_jvp: dens, vel, pres and vel1 required");
   BPK_REQUIRE(t_dens || t_vel || t_pres, "ns_full_step_jvp: no tangent given");
@@ -367,11 +350,7 @@ extern "C" int bpk_ns_full_step_jvp_f32(const float* dens, const float* vel, con
                                 B, g, dt, dx, stream);
     if (rc) return rc;
   } else {
-    hipError_t e = hipMemsetAsync(t_vel1, 0, 2 * P * sizeof(float), st);
-    if (e != hipSuccess) {
-      bpk::set_error("ns_full_step_jvp: %s", hipGetErrorString(e));
-      return BPK_ERR_LAUNCH;
-    }
+    NS_HIP_OK(hipMemsetAsync(t_vel1, 0, 2 * P * sizeof(float), st), "ns_full_step_jvp");
   }
   return launch_pres_dens_jvp(dens, vel1, t_dens, moves ? t_vel1 : nullptr, t_pres, t_dens1,
                               t_pres1, B, g, dt, dx, st, "ns_full_step_jvp(pressure+density)");

@@ -8,7 +8,7 @@
 // (d, (u, v), p).  The derivative is piecewise like the function: sgn(u), sgn(v) and the
 // upwind indices xm, ym are constants.
 //
-// A CIP site is linear in its ten gathered values (CipIn of ns_step.hip) with weights that
+// A CIP site is linear in its ten gathered values (CipVals of ns_common.h) with weights that
 // are polynomials in X = -u dt, Y = -v dt, dx and the two signs of the site's own velocity.
 // The adjoint with respect to f, fx, fy is therefore a gather: site s walks its 3x3
 // neighbourhood, recomputes each neighbour t's signs, mirrored xm / ym and weights from t's
@@ -21,7 +21,11 @@
 // Plain float32 with FMA contraction; none of the forward's exact-division machinery.
 // A velocity component exactly 0 makes the forward non-finite (a reference property); the
 // backward there is unspecified, but sgn = 0 gives xm = x, so every index stays in bounds.
-#include "ns_cip_deriv.h"  // Geo, VjpConst, clampx, sgn, NS_VJP_SITES, grid_for, cip_weights, cip_dxy
+//
+// ns_common.h (shared with the forward): Geo, clampx, sgn, CipVals, cip_gather, NS_GEO_CHECK,
+// NS_HIP_OK, velocity_stage_base.  ns_cip_deriv.h (shared with the tangent): VjpConst,
+// NS_VJP_SITES, grid_for, cip_weights, cip_dxy.
+#include "ns_cip_deriv.h"
 
 namespace {
 
@@ -195,6 +199,7 @@ __device__ inline float adj1d(const float* g, int64_t stride, int x, int n, floa
 
 // out[k] = a[k] + c[k] + scale (Dx^T gx[k] + Dy^T gy[k]) over P planes; a, c optional; every
 // operand has its own plane stride.  out may alias a or c (each site reads its own element).
+// Not k_gradient_adjoint of ns_step.hip: contraction on here, so the two round differently.
 __global__ __launch_bounds__(256) void k_grad_vjp(const float* gx, int64_t gxs, const float* gy,
                                                   int64_t gys, const float* a, int64_t as,
                                                   const float* c, int64_t cs, float* out,
@@ -211,20 +216,6 @@ __global__ __launch_bounds__(256) void k_grad_vjp(const float* gx, int64_t gxs, 
     out[b * os + s] = r;
   }
 }
-
-#define NS_VJP_GEO_CHECK(B, nx, ny)                                                            \
-  BPK_REQUIRE((B) >= 0 && (nx) >= 2 && (ny) >= 2, "ns_step vjp: need B >= 0 and planes >= 2x2 " \
-                                                  "(got B=%d nx=%d ny=%d)",                   \
-              (B), (nx), (ny))
-
-#define NS_HIP_OK(expr, what)                                                \
-  do {                                                                       \
-    hipError_t e_ = (expr);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      bpk::set_error("%s: %s", what, hipGetErrorString(e_));                 \
-      return BPK_ERR_LAUNCH;                                                 \
-    }                                                                        \
-  } while (0)
 
 int launch_grad_vjp(const float* gx, int64_t gxs, const float* gy, int64_t gys, const float* a,
                     int64_t as, const float* c, int64_t cs, float* out, int64_t os, int P,
@@ -243,20 +234,15 @@ int velocity_stage_vjp(const float* vel, const float* pres, const float* G, floa
                        float dt, float dx, void* stream) {
   const int64_t hw = g.hw, P = (int64_t)B * hw;
   hipStream_t st = bpk::as_stream(stream);
-  float* px = ws;
-  float* py = ws + P;
-  float* vel_n = ws + 2 * P;   // 2B planes
+  float* vel_n;                // first 4B planes: velocity_stage_base
   float* dfx = ws + 4 * P;     // 2B planes: d/dx of plane k of vel_n
   float* dfy = ws + 6 * P;
   float* H = ws + 8 * P;       // 2B planes: local terms
   float* gf = ws + 10 * P;     // 2B planes each
   float* gfx = ws + 12 * P;
   float* gfy = ws + 14 * P;
-  // un, vn and their stencil gradients, recomputed with the forward's own kernels (the same
-  // bits, hence the same signs, as the fused forward)
-  int rc = bpk_ns_gradient_f32(pres, hw, px, py, B, g.nx, g.ny, dx, stream);
-  if (rc) return rc;
-  rc = bpk_ns_vel_update_f32(vel, px, py, vel_n, B, g.nx, g.ny, dt, stream);
+  // un, vn and their stencil gradients, with the forward's own kernels
+  int rc = velocity_stage_base(vel, pres, ws, &vel_n, B, g, dt, dx, stream);
   if (rc) return rc;
   rc = bpk_ns_gradient_f32(vel_n, hw, dfx, dfy, 2 * B, g.nx, g.ny, dx, stream);
   if (rc) return rc;
@@ -301,7 +287,7 @@ extern "C" int64_t bpk_ns_vjp_workspace_bytes(int op, int B, int nx, int ny) {
 extern "C" int bpk_ns_gradient_vjp_f32(const float* gx, const float* gy, const float* base,
                                        float* out, int B, int nx, int ny, float dx, float scale,
                                        void* stream) {
-  NS_VJP_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step vjp", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(gx && gy && out, "ns_gradient_vjp: gx, gy and out required");
   const Geo g{nx, ny, (int64_t)nx * ny};
@@ -314,7 +300,7 @@ extern "C" int bpk_ns_cip_vjp_f32(const float* f, int64_t f_plane_stride, const 
                                   float* g_f, float* g_fx, float* g_fy, const float* g_vel_in,
                                   float* g_vel, int B, int nx, int ny, float dt, float dx,
                                   void* stream) {
-  NS_VJP_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step vjp", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(vel && g_out, "ns_cip_vjp: vel and g_out required");
   BPK_REQUIRE((g_f && g_fx && g_fy) || (!g_f && !g_fx && !g_fy),
@@ -343,7 +329,7 @@ extern "C" int bpk_ns_cip_vjp_f32(const float* f, int64_t f_plane_stride, const 
 extern "C" int bpk_ns_update_pressure_vjp_f32(const float* vel, const float* g_out, float* g_pres,
                                               const float* g_vel_in, float* g_vel, int B, int nx,
                                               int ny, float dt, float dx, void* stream) {
-  NS_VJP_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step vjp", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(vel && g_out, "ns_update_pressure_vjp: vel and g_out required");
   BPK_REQUIRE(g_pres || g_vel, "ns_update_pressure_vjp: no gradient requested");
@@ -359,7 +345,7 @@ extern "C" int bpk_ns_update_density_vjp_f32(const float* dens, const float* vel
                                              const float* g_vel_in, float* g_vel,
                                              void* workspace, int B, int nx, int ny, float dt,
                                              float dx, void* stream) {
-  NS_VJP_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step vjp", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(dens && vel && g_out, "ns_update_density_vjp: dens, vel and g_out required");
   BPK_REQUIRE(g_dens || g_vel, "ns_update_density_vjp: no gradient requested");
@@ -384,7 +370,7 @@ extern "C" int bpk_ns_update_velocity_vjp_f32(const float* vel, const float* pre
                                               const float* g_out, float* g_vel, float* g_pres,
                                               void* workspace, int B, int nx, int ny, float dt,
                                               float dx, void* stream) {
-  NS_VJP_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step vjp", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(vel && pres && g_out && g_vel,
               "ns_update_velocity_vjp: vel, pres, g_out and g_vel required");
@@ -399,7 +385,7 @@ extern "C" int bpk_ns_full_step_vjp_f32(const float* dens, const float* vel, con
                                         const float* g_vel1, const float* g_pres1, float* g_dens,
                                         float* g_vel, float* g_pres, void* workspace, int B,
                                         int nx, int ny, float dt, float dx, void* stream) {
-  NS_VJP_GEO_CHECK(B, nx, ny);
+  NS_GEO_CHECK("ns_step vjp", B, nx, ny);
   if (B == 0) return BPK_OK;
   BPK_REQUIRE(dens && vel && pres && vel1, "ns_full_step_vjp: dens, vel, pres and vel1 required");
   BPK_REQUIRE(g_dens1 || g_vel1 || g_pres1, "ns_full_step_vjp: no cotangent given");

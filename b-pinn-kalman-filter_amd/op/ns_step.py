@@ -43,18 +43,15 @@ def _geo(t):
     return B, nx, ny
 
 
-def _workspace(op, B, nx, ny, device):
-    nbytes = lib.bpk_ns_workspace_bytes(op, B, nx, ny)
+def _workspace(size_fn, op, B, nx, ny, device):
+    """size_fn: bpk_ns_workspace_bytes, bpk_ns_vjp_workspace_bytes or bpk_ns_jvp_workspace_bytes
+    (forward, adjoint, tangent)."""
+    nbytes = size_fn(op, B, nx, ny)
     return torch.empty(max(nbytes // 4, 1), device=device, dtype=torch.float32)
 
 
 def _wants_grad(*ts):
     return torch.is_grad_enabled() and any(t.requires_grad for t in ts)
-
-
-def _vjp_workspace(op, B, nx, ny, device):
-    nbytes = lib.bpk_ns_vjp_workspace_bytes(op, B, nx, ny)
-    return torch.empty(max(nbytes // 4, 1), device=device, dtype=torch.float32)
 
 
 def _cot(g):
@@ -73,7 +70,7 @@ def update_density(dens, vel, dt, dx):
 def _update_density(dens, vel, dt, dx):
     B, nx, ny = _geo(dens)
     out = torch.empty_like(dens)
-    ws = _workspace(0, B, nx, ny, dens.device)
+    ws = _workspace(lib.bpk_ns_workspace_bytes, 0, B, nx, ny, dens.device)
     check(lib.bpk_ns_update_density_f32(dens.data_ptr(), vel.data_ptr(), out.data_ptr(),
                                         ws.data_ptr(), B, nx, ny, float(dt), float(dx),
                                         stream_ptr(dens.device)), "ns_step.update_density")
@@ -93,7 +90,7 @@ def update_velocity(vel, pres, dt, dx, compat=True):
 def _update_velocity(vel, pres, dt, dx, compat):
     B, nx, ny = _geo(vel)
     out = torch.empty_like(vel)
-    ws = _workspace(1, B, nx, ny, vel.device)
+    ws = _workspace(lib.bpk_ns_workspace_bytes, 1, B, nx, ny, vel.device)
     check(lib.bpk_ns_update_velocity_f32(vel.data_ptr(), pres.data_ptr(), out.data_ptr(),
                                          ws.data_ptr(), B, nx, ny, float(dt), float(dx),
                                          int(bool(compat)), stream_ptr(vel.device)),
@@ -190,6 +187,35 @@ def once_differentiable(what):
     return deco
 
 
+def _density_vjp(dens, vel, g, need_dens, need_vel, dt, dx, what):
+    """Raw adjoint of update_density at (dens, vel): cotangent g -> (g_dens, g_vel), None
+    where not needed."""
+    B, nx, ny = _geo(dens)
+    g_dens = torch.empty_like(dens) if need_dens else None
+    g_vel = torch.empty_like(vel) if need_vel else None
+    ws = _workspace(lib.bpk_ns_vjp_workspace_bytes, 0, B, nx, ny, dens.device)
+    check(lib.bpk_ns_update_density_vjp_f32(dens.data_ptr(), vel.data_ptr(), g.data_ptr(),
+                                            ptr(g_dens), None, ptr(g_vel), ws.data_ptr(), B, nx,
+                                            ny, dt, dx, stream_ptr(dens.device)), what)
+    return g_dens, g_vel
+
+
+def _full_step_vjp(dens, vel, pres, v1, g_d1, g_v1, g_p1, need_dens, dt, dx, what):
+    """Raw adjoint of full_step(compat=False): contiguous cotangents (None = zero) ->
+    (g_dens or None, g_vel, g_pres); the velocity and pressure gradients come out of one pass
+    over the velocity stage."""
+    B, nx, ny = _geo(dens)
+    g_dens = torch.empty_like(dens) if need_dens else None
+    g_vel, g_pres = torch.empty_like(vel), torch.empty_like(pres)
+    ws = _workspace(lib.bpk_ns_vjp_workspace_bytes, 3, B, nx, ny, dens.device)
+    check(lib.bpk_ns_full_step_vjp_f32(dens.data_ptr(), vel.data_ptr(), pres.data_ptr(),
+                                       v1.data_ptr(), ptr(g_d1), ptr(g_v1), ptr(g_p1),
+                                       ptr(g_dens), g_vel.data_ptr(), g_pres.data_ptr(),
+                                       ws.data_ptr(), B, nx, ny, dt, dx,
+                                       stream_ptr(dens.device)), what)
+    return g_dens, g_vel, g_pres
+
+
 class _UpdateDensity(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dens, vel, dt, dx):
@@ -201,15 +227,9 @@ class _UpdateDensity(torch.autograd.Function):
     @once_differentiable("ns_step.update_density")
     def backward(ctx, g):
         dens, vel = ctx.saved_tensors
-        B, nx, ny = _geo(dens)
-        g = _cot(g)
-        g_dens = torch.empty_like(dens) if ctx.needs_input_grad[0] else None
-        g_vel = torch.empty_like(vel) if ctx.needs_input_grad[1] else None
-        ws = _vjp_workspace(0, B, nx, ny, dens.device)
-        check(lib.bpk_ns_update_density_vjp_f32(dens.data_ptr(), vel.data_ptr(), g.data_ptr(),
-                                                ptr(g_dens), None, ptr(g_vel), ws.data_ptr(), B,
-                                                nx, ny, ctx.dt, ctx.dx, stream_ptr(dens.device)),
-              "ns_step.update_density backward")
+        g_dens, g_vel = _density_vjp(dens, vel, _cot(g), ctx.needs_input_grad[0],
+                                     ctx.needs_input_grad[1], ctx.dt, ctx.dx,
+                                     "ns_step.update_density backward")
         return g_dens, g_vel, None, None
 
 
@@ -250,7 +270,7 @@ class _UpdateVelocity(torch.autograd.Function):
         g = _cot(g)
         g_vel = torch.empty_like(vel)  # the pressure gradient is computed from it
         g_pres = torch.empty_like(pres) if ctx.needs_input_grad[1] else None
-        ws = _vjp_workspace(1, B, nx, ny, vel.device)
+        ws = _workspace(lib.bpk_ns_vjp_workspace_bytes, 1, B, nx, ny, vel.device)
         check(lib.bpk_ns_update_velocity_vjp_f32(vel.data_ptr(), pres.data_ptr(), g.data_ptr(),
                                                  g_vel.data_ptr(), ptr(g_pres), ws.data_ptr(), B,
                                                  nx, ny, ctx.dt, ctx.dx, stream_ptr(vel.device)),
@@ -271,42 +291,24 @@ class _FullStep(torch.autograd.Function):
     @once_differentiable("ns_step.full_step")
     def backward(ctx, g_d1, g_v1, g_p1):
         dens, vel, pres, v1 = ctx.saved_tensors
-        B, nx, ny = _geo(dens)
         g_d1, g_v1, g_p1 = _cot(g_d1), _cot(g_v1), _cot(g_p1)
         if g_d1 is None and g_v1 is None and g_p1 is None:
             return None, None, None, None, None
         need = ctx.needs_input_grad
-        st = stream_ptr(dens.device)
         if not (need[1] or need[2]):  # dens' is the only output that depends on dens
             if g_d1 is None:
                 return None, None, None, None, None
-            g_dens = torch.empty_like(dens)
-            ws = _vjp_workspace(0, B, nx, ny, dens.device)
-            check(lib.bpk_ns_update_density_vjp_f32(dens.data_ptr(), v1.data_ptr(),
-                                                    g_d1.data_ptr(), g_dens.data_ptr(), None,
-                                                    None, ws.data_ptr(), B, nx, ny, ctx.dt,
-                                                    ctx.dx, st), "ns_step.full_step backward")
+            g_dens, _ = _density_vjp(dens, v1, g_d1, True, False, ctx.dt, ctx.dx,
+                                     "ns_step.full_step backward")
             return g_dens, None, None, None, None
-        g_dens = torch.empty_like(dens) if need[0] else None
-        # velocity and pressure gradients come out of one pass over the velocity stage
-        g_vel, g_pres = torch.empty_like(vel), torch.empty_like(pres)
-        ws = _vjp_workspace(3, B, nx, ny, dens.device)
-        check(lib.bpk_ns_full_step_vjp_f32(dens.data_ptr(), vel.data_ptr(), pres.data_ptr(),
-                                           v1.data_ptr(), ptr(g_d1), ptr(g_v1), ptr(g_p1),
-                                           ptr(g_dens), g_vel.data_ptr(), g_pres.data_ptr(),
-                                           ws.data_ptr(), B, nx, ny, ctx.dt, ctx.dx, st),
-              "ns_step.full_step backward")
+        g_dens, g_vel, g_pres = _full_step_vjp(dens, vel, pres, v1, g_d1, g_v1, g_p1, need[0],
+                                               ctx.dt, ctx.dx, "ns_step.full_step backward")
         return g_dens, (g_vel if need[1] else None), (g_pres if need[2] else None), None, None
 
 
 # ---- functional linear models at a given base state (csrc/ns_step_jvp.hip and
 # csrc/ns_step_vjp.hip), for callers that apply M or M^T many times at stored states (the
 # inner loop of incremental 4D-Var).  compat=False only; outputs carry no autograd graph.
-def _jvp_workspace(op, B, nx, ny, device):
-    nbytes = lib.bpk_ns_jvp_workspace_bytes(op, B, nx, ny)
-    return torch.empty(max(nbytes // 4, 1), device=device, dtype=torch.float32)
-
-
 def _linear_args(name, primals, others, kind):
     """Check and detach the primals and their tangents / cotangents (`others`, aligned with
     `primals`, None = zero); at least one of `others` is required."""
@@ -320,6 +322,15 @@ def _linear_args(name, primals, others, kind):
                                f"got {list(t.shape)} for {list(p.shape)}")
     return ([p.detach().contiguous() for p in primals],
             [None if t is None else t.detach().contiguous() for t in others])
+
+
+def _base_v1(name, v1, vel):
+    """The base step's velocity output as the linear models take it."""
+    _check(name, v1)
+    if v1.shape != vel.shape:
+        raise RuntimeError(f"ns_step.{name}: v1 must have the shape of vel, got "
+                           f"{list(v1.shape)} for {list(vel.shape)}")
+    return v1.detach().contiguous()
 
 
 def _same_geo(name, *ts):
@@ -336,7 +347,7 @@ def update_density_jvp(dens, vel, t_dens, t_vel, dt, dx):
     _same_geo("update_density_jvp", dens, vel)
     B, nx, ny = _geo(dens)
     out = torch.empty_like(dens)
-    ws = _jvp_workspace(0, B, nx, ny, dens.device)
+    ws = _workspace(lib.bpk_ns_jvp_workspace_bytes, 0, B, nx, ny, dens.device)
     check(lib.bpk_ns_update_density_jvp_f32(dens.data_ptr(), vel.data_ptr(), ptr(t_dens),
                                             ptr(t_vel), out.data_ptr(), ws.data_ptr(), B, nx, ny,
                                             float(dt), float(dx), stream_ptr(dens.device)),
@@ -351,7 +362,7 @@ def update_velocity_jvp(vel, pres, t_vel, t_pres, dt, dx):
     _same_geo("update_velocity_jvp", vel, pres)
     B, nx, ny = _geo(vel)
     out = torch.empty_like(vel)
-    ws = _jvp_workspace(1, B, nx, ny, vel.device)
+    ws = _workspace(lib.bpk_ns_jvp_workspace_bytes, 1, B, nx, ny, vel.device)
     check(lib.bpk_ns_update_velocity_jvp_f32(vel.data_ptr(), pres.data_ptr(), ptr(t_vel),
                                              ptr(t_pres), out.data_ptr(), ws.data_ptr(), B, nx,
                                              ny, float(dt), float(dx), stream_ptr(vel.device)),
@@ -384,14 +395,10 @@ def full_step_jvp(dens, vel, pres, t_dens, t_vel, t_pres, dt, dx, v1=None):
     if v1 is None:
         v1 = _full_step(dens, vel, pres, dt, dx, False, None)[1]
     else:
-        _check("full_step_jvp", v1)
-        if v1.shape != vel.shape:
-            raise RuntimeError(f"ns_step.full_step_jvp: v1 must have the shape of vel, got "
-                               f"{list(v1.shape)} for {list(vel.shape)}")
-        v1 = v1.detach().contiguous()
+        v1 = _base_v1("full_step_jvp", v1, vel)
     B, nx, ny = _geo(dens)
     t_d1, t_v1, t_p1 = torch.empty_like(dens), torch.empty_like(vel), torch.empty_like(pres)
-    ws = _jvp_workspace(3, B, nx, ny, dens.device)
+    ws = _workspace(lib.bpk_ns_jvp_workspace_bytes, 3, B, nx, ny, dens.device)
     check(lib.bpk_ns_full_step_jvp_f32(dens.data_ptr(), vel.data_ptr(), pres.data_ptr(),
                                        v1.data_ptr(), ptr(t_dens), ptr(t_vel), ptr(t_pres),
                                        t_d1.data_ptr(), t_v1.data_ptr(), t_p1.data_ptr(),
@@ -408,20 +415,9 @@ def full_step_vjp(dens, vel, pres, v1, g_d1, g_v1, g_p1, dt, dx):
     (dens, vel, pres), (g_d1, g_v1, g_p1) = _linear_args(
         "full_step_vjp", (dens, vel, pres), (g_d1, g_v1, g_p1), "cotangent")
     _same_geo("full_step_vjp", dens, vel, pres)
-    _check("full_step_vjp", v1)
-    if v1.shape != vel.shape:
-        raise RuntimeError(f"ns_step.full_step_vjp: v1 must have the shape of vel, got "
-                           f"{list(v1.shape)} for {list(vel.shape)}")
-    v1 = v1.detach().contiguous()
-    B, nx, ny = _geo(dens)
-    g_dens, g_vel, g_pres = torch.empty_like(dens), torch.empty_like(vel), torch.empty_like(pres)
-    ws = _vjp_workspace(3, B, nx, ny, dens.device)
-    check(lib.bpk_ns_full_step_vjp_f32(dens.data_ptr(), vel.data_ptr(), pres.data_ptr(),
-                                       v1.data_ptr(), ptr(g_d1), ptr(g_v1), ptr(g_p1),
-                                       g_dens.data_ptr(), g_vel.data_ptr(), g_pres.data_ptr(),
-                                       ws.data_ptr(), B, nx, ny, float(dt), float(dx),
-                                       stream_ptr(dens.device)), "ns_step.full_step_vjp")
-    return g_dens, g_vel, g_pres
+    v1 = _base_v1("full_step_vjp", v1, vel)
+    return _full_step_vjp(dens, vel, pres, v1, g_d1, g_v1, g_p1, True, float(dt), float(dx),
+                          "ns_step.full_step_vjp")
 
 
 # low-level kernels (one launch each), exposed for tests and custom pipelines

@@ -29,6 +29,7 @@ from typing import Optional
 import torch
 
 from . import simulator
+from .ukf_utils import valid_steps
 
 
 @dataclass
@@ -79,12 +80,7 @@ class LETKF:
         else:
             raise ValueError(f"LETKF: unknown taper {taper!r}")
         self.radius = self.taper.shape[0] // 2
-        if step_fn is None:
-            from op import ns_step
-
-            def step_fn(f, v, p):
-                return ns_step.full_step(f, v, p, self.dt, self.dx, compat=False)
-        self.step_fn = step_fn
+        self.step_fn = simulator.default_step(self.dt, self.dx) if step_fn is None else step_fn
         self.analysis_fn = K.analysis if analysis_fn is None else analysis_fn
         self.ens = None
 
@@ -139,11 +135,9 @@ class LETKF:
         """`steps_per_frame` simulator steps of every member."""
         ens = self._need()
         B, m, C, H, W = ens.shape
-        planes = ens.view(B * m, C, H, W)
-        f, v, p = planes[:, 0:1], planes[:, 1:3], planes[:, 3:4]
-        for _ in range(self.steps_per_frame):
-            f, v, p = self.step_fn(f.contiguous(), v.contiguous(), p.contiguous())
-        self.ens = torch.cat([f, v, p], dim=1).view(B, m, C, H, W)
+        fvp = simulator.split_state(ens.view(B * m, C, H, W))
+        fvp = simulator.advance(self.step_fn, *fvp, self.steps_per_frame)
+        self.ens = simulator.join_state(*fvp).view(B, m, C, H, W)
         return self.ens
 
     @torch.no_grad()
@@ -176,13 +170,12 @@ class LETKF:
         ensemble.  weights: as `analyze` (broadcast over the frames).  valid: None, bool [T] or
         bool [T, B] as `UKF.filter` takes it; a missing frame is forecast only.
         -> EnsembleHistory."""
-        from .ukf import SquareRootUKF
         ens = self._need()
         if obsv_seq.ndim != 5 or tuple(obsv_seq.shape[1:]) != (ens.shape[0],) + tuple(ens.shape[2:]):
             raise ValueError(f"LETKF.filter: obsv_seq must be [T, B, C, H, W] of the ensemble, got "
                              f"{list(obsv_seq.shape)}")
         T, B = obsv_seq.shape[:2]
-        steps = SquareRootUKF._valid_steps(valid, T, B)
+        steps = valid_steps(valid, T, B)
         means, spreads, fmeans, flagged, fens, aens = [], [], [], [], [], []
         for t in range(T):
             self.forecast()

@@ -27,6 +27,8 @@ from dataclasses import dataclass
 
 import torch
 
+from op import ns_step
+
 from . import simulator
 
 
@@ -88,24 +90,23 @@ class FourDVar:
             raise ValueError("FourDVar: steps_per_frame must be >= 1")
         self.steps_per_frame = int(steps_per_frame)
         self.dt, self.dx = float(dt), float(dx)
-        if step_fn is None:
-            from op import ns_step
-
-            def step_fn(f, v, p):
-                return ns_step.full_step(f, v, p, self.dt, self.dx, compat=False)
-        self.step_fn = step_fn
+        self.step_fn = simulator.default_step(self.dt, self.dx) if step_fn is None else step_fn
 
     def rollout(self, state0, T):
         """-> [T, B, 4, H, W]: frame t (0-based) is the state after (t + 1) * steps_per_frame
         steps; differentiable with respect to state0."""
+        return self._frames(state0, T, None)
+
+    def _frames(self, state0, T, bases):
+        """`rollout`; bases: None, or a list that receives the base state (d, v, p, v1) of
+        every sub-step in order (`simulator.advance`)."""
         if state0.ndim != 4 or state0.shape[1] != 4:
             raise ValueError(f"FourDVar: state must be [B, 4, H, W], got {list(state0.shape)}")
-        f, v, p = state0[:, 0:1], state0[:, 1:3], state0[:, 3:4]
+        fvp = simulator.split_state(state0)
         frames = []
         for _ in range(int(T)):
-            for _ in range(self.steps_per_frame):
-                f, v, p = self.step_fn(f.contiguous(), v.contiguous(), p.contiguous())
-            frames.append(torch.cat([f, v, p], dim=1))
+            fvp = simulator.advance(self.step_fn, *fvp, self.steps_per_frame, bases)
+            frames.append(simulator.join_state(*fvp))
         return torch.stack(frames)
 
     def _cost(self, state0, obsv_seq, weights, background, background_weights):
@@ -174,44 +175,27 @@ class IncrementalFourDVar(FourDVar):
                  tangent_fn=None, adjoint_fn=None):
         super().__init__(steps_per_frame, dt, dx, step_fn)
         if tangent_fn is None:
-            from op import ns_step
-
             def tangent_fn(d, v, p, v1, td, tv, tp):
                 return ns_step.full_step_jvp(d, v, p, td, tv, tp, self.dt, self.dx, v1=v1)
         if adjoint_fn is None:
-            from op import ns_step
-
             def adjoint_fn(d, v, p, v1, gd1, gv1, gp1):
                 return ns_step.full_step_vjp(d, v, p, v1, gd1, gv1, gp1, self.dt, self.dx)
         self.tangent_fn, self.adjoint_fn = tangent_fn, adjoint_fn
 
-    @staticmethod
-    def _split(x):
-        return x[:, 0:1].contiguous(), x[:, 1:3].contiguous(), x[:, 3:4].contiguous()
-
     def _linearize(self, state0, T):
         """Nonlinear rollout from state0 -> (frames [T, B, 4, H, W], the base state
         (d, v, p, v1) of every sub-step in order)."""
-        if state0.ndim != 4 or state0.shape[1] != 4:
-            raise ValueError(f"FourDVar: state must be [B, 4, H, W], got {list(state0.shape)}")
-        f, v, p = self._split(state0)
-        states, frames = [], []
-        for _ in range(int(T)):
-            for _ in range(self.steps_per_frame):
-                f1, v1, p1 = self.step_fn(f, v, p)
-                states.append((f, v, p, v1))
-                f, v, p = f1.contiguous(), v1.contiguous(), p1.contiguous()
-            frames.append(torch.cat([f, v, p], dim=1))
-        return torch.stack(frames), states
+        states = []
+        return self._frames(state0, T, states), states
 
     def _tangent_sweep(self, states, dx0):
         """M_t dx0 for every frame t -> [T, B, 4, H, W]."""
-        t = self._split(dx0)
+        t = simulator.split_state(dx0)
         frames = []
         for i, base in enumerate(states):
             t = self.tangent_fn(*base, *t)
             if (i + 1) % self.steps_per_frame == 0:
-                frames.append(torch.cat(t, dim=1))
+                frames.append(simulator.join_state(*t))
         return torch.stack(frames)
 
     def _adjoint_sweep(self, states, cots):
@@ -220,7 +204,8 @@ class IncrementalFourDVar(FourDVar):
         for i in range(len(states) - 1, -1, -1):
             if (i + 1) % self.steps_per_frame == 0:
                 lam = lam + cots[(i + 1) // self.steps_per_frame - 1]
-            lam = torch.cat(self.adjoint_fn(*states[i], *self._split(lam)), dim=1)
+            lam = simulator.join_state(
+                *self.adjoint_fn(*states[i], *simulator.split_state(lam)))
         return lam
 
     def fit(self, obsv_seq, weights, background, background_weights, outer=3, inner=10):

@@ -21,6 +21,39 @@ dt = 0.0005 * 5
 dx = 1 / 200
 
 
+# ---- the field state of the filters and the variational fits (UKF, LETKF, 4D-Var):
+# [B, 4, H, W] with channels (f, u, v, p)
+def split_state(x):
+    """[B, 4, H, W] -> contiguous (f [B, 1, H, W], v [B, 2, H, W], p [B, 1, H, W])."""
+    return x[:, 0:1].contiguous(), x[:, 1:3].contiguous(), x[:, 3:4].contiguous()
+
+
+def join_state(f, v, p):
+    """Inverse of `split_state`."""
+    return torch.cat([f, v, p], dim=1)
+
+
+def default_step(dt=dt, dx=dx):
+    """step_fn(f, v, p) -> (f', v', p'): `ns_step.full_step(compat=False)`, the differentiable
+    step (HIP tensors only)."""
+    def step_fn(f, v, p):
+        return ns_step.full_step(f, v, p, dt, dx, compat=False)
+    return step_fn
+
+
+def advance(step_fn, f, v, p, n, bases=None):
+    """n steps of step_fn from (f, v, p), each on contiguous tensors -> (f, v, p).  bases: a
+    list that receives every step's base state (f, v, p, v1), v1 being that step's velocity
+    output -- what the step's tangent and adjoint take."""
+    for _ in range(int(n)):
+        f, v, p = f.contiguous(), v.contiguous(), p.contiguous()
+        f1, v1, p1 = step_fn(f, v, p)
+        if bases is not None:
+            bases.append((f, v, p, v1))
+        f, v, p = f1, v1, p1
+    return f, v, p
+
+
 def _prep(data, device):
     return torch.from_numpy(np.ascontiguousarray(data[:, 8:200, 4:-4])).to(device).unsqueeze(0)
 

@@ -54,7 +54,9 @@ import torch.nn as nn
 from op import ukf as K
 
 from .pinn import B_PINN
-from .ukf_utils import IdentityKFMeasure, InpaintKFMeasure, NSDynamics, patch, unpatch
+from .simulator import join_state
+from .ukf_utils import (IdentityKFMeasure, InpaintKFMeasure, NSDynamics, patch, unpatch,
+                        valid_steps)
 
 
 class FilterHistory:
@@ -233,7 +235,7 @@ class SquareRootUKF(nn.Module):
             raise ValueError(f"SquareRootUKF.filter: {len(controls)} controls for {T} observations")
         N, n = self.belief_mean.shape
         dev = self.belief_mean.device
-        steps = self._valid_steps(valid, T, N)
+        steps = valid_steps(valid, T, N)
         keep = self.diagnostics or self.gate is not None or valid is not None
         means, trils, pmeans, ptrils = [self.belief_mean], [self.belief_scale_tril], [], []
         nis, logliks, accepted = [], [], []
@@ -261,30 +263,7 @@ class SquareRootUKF(nn.Module):
                              torch.stack(ptrils) if T else torch.empty(0, N, n, n, device=dev),
                              controls, **stats)
 
-    @staticmethod
-    def _valid_steps(valid, T, N):
-        """`filter`'s `valid` -> T entries, each True (plain update), False (skip) or a bool
-        [N] device mask."""
-        if valid is None:
-            return [True] * T
-        if torch.is_tensor(valid):
-            if valid.dtype != torch.bool or valid.ndim not in (1, 2) or valid.shape[0] != T:
-                raise ValueError(f"SquareRootUKF.filter: valid must be bool [{T}] or "
-                                 f"[{T}, {N}], got {valid.dtype} {list(valid.shape)}")
-            if valid.ndim == 1 and not valid.is_cuda:
-                valid = valid.tolist()
-            elif valid.ndim == 1:  # on the device: never read, becomes a mask per step
-                valid = valid.unsqueeze(1).expand(T, N)
-        steps = []
-        if len(valid) != T:
-            raise ValueError(f"SquareRootUKF.filter: {len(valid)} valid entries for {T} "
-                             "observations")
-        for v in valid:
-            if torch.is_tensor(v):
-                steps.append(v if v.ndim else v.expand(N))
-            else:
-                steps.append(v is not None and bool(v))
-        return steps
+    _valid_steps = staticmethod(valid_steps)  # its earlier home; `LETKF.filter` shares it
 
     @torch.no_grad()
     def smooth(self, history):
@@ -481,7 +460,7 @@ class PINN_KF(nn.Module):
         self.f_prev = None
 
     def initialize(self, f, v, p, var=1e-2):
-        state = patch(torch.cat([f, v, p], dim=1), self.patch_size)
+        state = patch(join_state(f, v, p), self.patch_size)
         self.ukf.initialize(state, var)
         self.f_prev = f
 

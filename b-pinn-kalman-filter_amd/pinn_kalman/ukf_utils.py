@@ -19,6 +19,8 @@ import torch.nn as nn
 
 from op import ns_step
 
+from .simulator import join_state, split_state
+
 DT = 0.0005 * 5  # reference ukf_utils.py:105-106 (the simulator's dt / dx)
 DX = 1 / 200
 
@@ -38,6 +40,31 @@ def unpatch(x, p_size, f_size, channel_num=6):
     x = x.reshape(channel_num, -1, num, num, p_size, p_size)  # (c, b, i, j, a, b')
     x = x.permute(0, 1, 2, 4, 3, 5).reshape(channel_num, -1, f_size, f_size)
     return x.transpose(0, 1)
+
+
+def valid_steps(valid, T, N):
+    """The `valid` of `SquareRootUKF.filter` / `LETKF.filter` -> T entries, each True (plain
+    update), False (skip) or a bool [N] device mask."""
+    if valid is None:
+        return [True] * T
+    if torch.is_tensor(valid):
+        if valid.dtype != torch.bool or valid.ndim not in (1, 2) or valid.shape[0] != T:
+            raise ValueError(f"SquareRootUKF.filter: valid must be bool [{T}] or "
+                             f"[{T}, {N}], got {valid.dtype} {list(valid.shape)}")
+        if valid.ndim == 1 and not valid.is_cuda:
+            valid = valid.tolist()
+        elif valid.ndim == 1:  # on the device: never read, becomes a mask per step
+            valid = valid.unsqueeze(1).expand(T, N)
+    steps = []
+    if len(valid) != T:
+        raise ValueError(f"SquareRootUKF.filter: {len(valid)} valid entries for {T} "
+                         "observations")
+    for v in valid:
+        if torch.is_tensor(v):
+            steps.append(v if v.ndim else v.expand(N))
+        else:
+            steps.append(v is not None and bool(v))
+    return steps
 
 
 class NSDynamics(nn.Module):
@@ -63,10 +90,9 @@ class NSDynamics(nn.Module):
         return unpatch(x, self.dim, self.size, 4)
 
     def forward(self, initial_states, controls=None):
-        u = self.unpatch(initial_states)
-        f, v, p = u[:, 0:1].contiguous(), u[:, 1:3].contiguous(), u[:, 3:4].contiguous()
+        f, v, p = split_state(self.unpatch(initial_states))
         f, v, p = ns_step.full_step(f, v, p, DT, DX, compat=self.compat)
-        state = patch(torch.cat([f, v, p], dim=1), self.dim)
+        state = patch(join_state(f, v, p), self.dim)
         # one 1e-8 I shared by every row (a stride-0 view: the sigma-point batch of the shipped
         # config has 297216 rows, 4.9 GB if repeated)
         uncer = (torch.eye(self.dim ** 2, device=state.device) * 1e-8).unsqueeze(0).expand(

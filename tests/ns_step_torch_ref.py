@@ -356,3 +356,40 @@ def twin_truth64():
         fd = FourDVar(steps_per_frame=1, dt=DT, dx=DX, step_fn=step_fn)
         _CACHE["twin64"] = twin_run(fd, torch.float64, torch.device("cpu"))
     return _CACHE["twin64"]
+
+
+# ------------------------------------------------------------------ C ABI geometry refusals
+BAD_GEOMETRIES = [(2, 1, 5), (2, 4, 1), (-1, 4, 5), (2, 65536, 32768)]  # (B, nx, ny)
+
+
+def refused_geometries(dll, select):
+    """Call every compute entry `int bpk_ns_*` of include/bpk.h whose name `select` accepts
+    with each of BAD_GEOMETRIES and dummy non-NULL pointers (validation returns before a
+    pointer or the device is touched): status 1 and a message naming the planes.
+    -> the names called."""
+    import re
+
+    from op import _lib
+    with open(_lib.HEADER_PATH) as fh:
+        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
+    names = []
+    for ret, name, args in _lib._PROTO_RE.findall(text):
+        if ret != "int" or not name.startswith("bpk_ns_") or not select(name):
+            continue
+        params = [" ".join(a.split()) for a in args.split(",")]
+        for B, nx, ny in BAD_GEOMETRIES:
+            geo, vals = {"B": B, "nx": nx, "ny": ny}, []
+            for prm in params:
+                pname = prm.rsplit(" ", 1)[1]
+                if pname == "stream":
+                    vals.append(None)
+                elif "*" in prm:
+                    vals.append(1)
+                elif pname in geo:
+                    vals.append(geo[pname])
+                else:  # dt, dx, scale; a plane stride; compat
+                    vals.append(0.1 if prm.startswith("float") else 0)
+            rc = getattr(dll, name)(*vals)
+            assert rc == 1 and b"planes" in dll.bpk_last_error(), (name, B, nx, ny)
+        names.append(name)
+    return names

@@ -249,8 +249,10 @@ def _ns_fields(B, nx, ny, seed=0):
     return f, v, p
 
 
+# (2, 2, 2), (2, 3, 2): every site on two borders; (2, 65, 6): a partial second tile in x of the
+# LDS-tiled velocity kernel (64 x 4)
 @pytest.mark.parametrize("B,nx,ny", [(1, 16, 16), (3, 32, 32), (4, 24, 40), (1100, 8, 8),
-                                      (2, 192, 192)])
+                                      (2, 192, 192), (2, 2, 2), (2, 3, 2), (2, 65, 6)])
 @pytest.mark.parametrize("compat", [True, False])
 def test_ns_step_bit_exact_vs_c_oracle(hip, B, nx, ny, compat):
     from op import ns_step

@@ -141,6 +141,7 @@ def test_jvp_argument_errors_are_reported_without_a_device():
         assert dll.bpk_ns_jvp_workspace_bytes(op, 4, 8, 8) > 0
     assert dll.bpk_ns_jvp_workspace_bytes(2, 4, 8, 8) == 0
     assert dll.bpk_ns_jvp_workspace_bytes(1, 4, 8, 8) == 6 * 4 * 64 * 4
+    assert len(R.refused_geometries(dll, lambda name: "_jvp_" in name)) == 4
 
 
 def test_new_ops_refuse_cpu_tensors():

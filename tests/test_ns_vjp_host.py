@@ -146,6 +146,9 @@ def test_vjp_argument_errors_are_reported_without_a_device():
     assert dll.bpk_ns_vjp_workspace_bytes(1, 4, 8, 8) == 16 * 4 * 64 * 4
     assert dll.bpk_ns_vjp_workspace_bytes(2, 4, 8, 8) == 0
     assert dll.bpk_ns_vjp_workspace_bytes(3, 4, 8, 8) == 18 * 4 * 64 * 4
+    # the forward's and the adjoint's entries share one geometry check: nx = 1, ny = 1, B = -1
+    # and a plane of 2^31 sites, whose in-plane index no longer fits the kernels' int
+    assert len(R.refused_geometries(dll, lambda name: "_jvp_" not in name)) == 16
 
 
 def test_ops_keep_refusing_cpu_tensors_with_grad():
