@@ -204,6 +204,22 @@ __device__ inline void merge_stats(float& m, float& m2, float mo, float m2o, flo
   m = 0.5f * (m + mo);
 }
 
+// 4 x 4 transpose inside a DPP quad: lane t (= lane & 3) gives a[r] and gets a[s] = the a[t] of
+// the quad's lane s.  Two butterfly steps (lanes xor 1 on the pairs (0, 1), (2, 3), then lanes
+// xor 2 on (0, 2), (1, 3)): values are moved, never combined.
+template <int CTRL>
+__device__ inline void quad_swap(float& lo, float& hi, bool upper) {
+  const float plo = dpp_f<CTRL>(lo), phi = dpp_f<CTRL>(hi);
+  lo = upper ? phi : lo;
+  hi = upper ? hi : plo;
+}
+__device__ inline void quad_transpose(float (&a)[4], int t) {
+  quad_swap<0xB1>(a[0], a[1], t & 1);
+  quad_swap<0xB1>(a[2], a[3], t & 1);
+  quad_swap<0x4E>(a[0], a[2], t & 2);
+  quad_swap<0x4E>(a[1], a[3], t & 2);
+}
+
 // Per-workgroup phase timestamps (diagnostic build only, -DWINO_TIMING; tools/wino_timing.py):
 // wall clock (100 MHz) at entry, once the prologue's loads have landed, after the first patch
 // stores, at the start of the chunk loop, after it and after the epilogue (wave 0's view), the
@@ -909,9 +925,13 @@ __global__ __launch_bounds__(512, 1) void wino_f23_k16_kernel(
 //     a record: wave w transforms half h = w & 1 (slots 2 h, 2 h + 1: the F(2,3) row pass of
 //     patch rows h .. h + 2, then the F(4,3) pass along both rows) of channels 4 kq + (w >> 1),
 //     so a read group's two kq values sit 960 dwords apart (= 0 mod 64 banks).
-//   * accumulators: acc[24] f4 = 96 registers: lane (kq, jj) holds, for cout cout_w + jj, the 24
-//     points of the 4 tiles of tile row kq -- after the output transform 2 rows x 16 contiguous
-//     pixels, 8 f4 strips as k16_item (same stores, skip loads and statistics strips).
+//   * accumulators: acc[24] f4 = 96 registers.  The filter fragment is the MFMA's A operand and
+//     the V fragment its B operand (both are held as index lane & 15, k = lane >> 4), so D is
+//     [cout][tile]: lane (kq, jj) holds the 24 points of tile jj = 4 tty + ttx for the couts
+//     cout_w + 4 kq + r, r = 0..3 -- after the output transform one f4 strip per (r, h).  The
+//     four lanes of a quad (ttx) then write the 64 contiguous bytes of one region row: a wave's
+//     store or skip load is 16 segments of 64 B (4 couts x 4 tile rows), not 64 pieces of 16 B
+//     (measurements: profiles/wino_epilogue/).  The statistics keep the merge order of k16_item.
 //   * U operands: uo[2][6] f4, one f4 per 4 MFMAs, refilled two k-steps ahead right after use;
 //     U24 is laid out per 16-cout group and fragment so that a wave's load is 4 x 256 B.
 // LDS: 2 x 15 KB patches + 2 x 28 KB V + the GroupNorm table (8 KB) = 94 KB.
@@ -1035,7 +1055,8 @@ __device__ __forceinline__ void k16_item24(
       sp[pdst + c * (kPR * kPCp)] = pin ? v : 0.f;
     }
   };
-  // B operands: uo[ks & 1][q] = points 4q..4q + 3 of U24 (cin c0 + 4 ks + kq, cout cout_w + jj),
+  // filter operands (the MFMA's A, rows of D = couts): uo[ks & 1][q] = points 4q..4q + 3 of U24
+  // (cin c0 + 4 ks + kq, cout cout_w + jj),
   // at [cin][cout_w / 16][q][jj] (wino_filter24_kernel): 256 contiguous bytes per kq
   f4(&uo)[2][6] = carry.uo;
   const int uoff = ((kq * g.Cout + cout_w) * 24 + jj * 4) * 4;
@@ -1124,7 +1145,8 @@ __device__ __forceinline__ void k16_item24(
   __syncthreads();
   WINO_TS_AT(b, 1);
 
-  // A operands: points 4q..4q + 3 of the record (cin 4 ks + kq, tile jj), in a ring of four
+  // V operands (the MFMA's B, columns of D = tiles): points 4q..4q + 3 of the record (cin
+  // 4 ks + kq, tile jj), in a ring of four
   // registers quads over the chunk's 24 (ks, q) fragments: fragment i sits in a[i & 3] and is
   // replaced by fragment i + 4 right after its MFMAs (12 MFMAs before that one is used)
   f4 a[4];
@@ -1161,7 +1183,7 @@ __device__ __forceinline__ void k16_item24(
 #pragma unroll
         for (int pp = 0; pp < 4; ++pp)
           acc[4 * q + pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-              a[fi & 3][pp], uo[ks & 1][q][pp],
+              uo[ks & 1][q][pp], a[fi & 3][pp],
               (FIRST && ks == 0) ? f4{0.f, 0.f, 0.f, 0.f} : acc[4 * q + pp], 0, 0, 0);
         if (fi + 4 < 24) a[fi & 3] = a_src(sv, (fi + 4) / 6)[(fi + 4) % 6];
         // k-step ks + 2 of this chunk, or ks - 2 of the next; after the last chunk (UNEXT) of
@@ -1221,62 +1243,94 @@ __device__ __forceinline__ void k16_item24(
   }
   WINO_TS_AT(b, 3);
 
-  // output transform straight from registers: tile row kq, tiles rg = 0..3 -> output rows
-  // oy0 + 2 kq + h, one f4 strip per tile
+  // output transform straight from registers: lane (kq, jj = 4 tty + ttx) holds tile (tty, ttx)
+  // of couts co0 .. co0 + 3 (register r): per (r, h) one f4 strip of output row oy0 + 2 tty + h,
+  // so the four lanes of a quad write 64 contiguous bytes and a wave's store is 16 such segments
   const float rdiv = 1.f / g.div;
   if (cout_w < g.CoutS) {
-    const int co = cout_w + jj;
-    const float bv = bias ? bias[co] : 0.f;
-    const int64_t obase = ((int64_t)(ks_idx * g.N + n) * g.CoutS + co) * plane +
-                          (int64_t)(oy0 + 2 * kq) * g.W + ox0;
-    float lm = 0.f, lm2 = 0.f;
+    const int co0 = cout_w + 4 * kq;
+    f4 bv = f4{0.f, 0.f, 0.f, 0.f};
+    if (bias) bv = f4{bias[co0], bias[co0 + 1], bias[co0 + 2], bias[co0 + 3]};
+    const int64_t obase = ((int64_t)(ks_idx * g.N + n) * g.CoutS + co0) * plane +
+                          (int64_t)(oy0 + 2 * tty) * g.W + ox0 + 4 * ttx;
+    float sm[2][4], sm2[2][4];  // strip (mean, M2) of (h, cout r)
     // residual tail: all eight skip vectors of this lane requested before the first is used
-    f4 skv[2][4];
+    f4 skv[4][2];
     if (skip) {
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
+      for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int rg = 0; rg < 4; ++rg)
-          skv[h][rg] = *reinterpret_cast<const f4*>(&skip[obase + (int64_t)h * g.W + 4 * rg]);
+        for (int h = 0; h < 2; ++h)
+#ifdef WINO_F24_EPI_ONE_STORE
+          skv[r][h] = f4{0.f, 0.f, 0.f, 0.f};
+#else
+          skv[r][h] = *reinterpret_cast<const f4*>(&skip[obase + r * plane + (int64_t)h * g.W]);
+#endif
     }
+#ifdef WINO_F24_EPI_ONE_STORE
+    // timing diagnostic only (wrong results; tools/build_wino_timing.sh NAME -D...=1): the eight
+    // strips summed into one store per lane and no skip loads -- what is left of epilogue + gap
+    // then is not the stores' or the loads' (profiles/wino_epilogue/README.md, section 1)
+    f4 vsum = f4{0.f, 0.f, 0.f, 0.f};
+#endif
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int r = 0; r < 4; ++r) {
 #pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
+      for (int h = 0; h < 2; ++h) {
         float t[6], yv[4];
 #pragma unroll
         for (int j = 0; j < 6; ++j)
-          t[j] = wino24_out_rows(acc[j][rg], acc[6 + j][rg], acc[12 + j][rg], acc[18 + j][rg], h);
+          t[j] = wino24_out_rows(acc[j][r], acc[6 + j][r], acc[12 + j][r], acc[18 + j][r], h);
         wino24_out_cols(t, yv);
-        f4 v = f4{yv[0] + bv, yv[1] + bv, yv[2] + bv, yv[3] + bv};
-        const int64_t o = obase + (int64_t)h * g.W + 4 * rg;
+        f4 v = f4{yv[0] + bv[r], yv[1] + bv[r], yv[2] + bv[r], yv[3] + bv[r]};
         if (skip) {
-          const f4 sk = skv[h][rg];
+          const f4 sk = skv[r][h];
 #pragma unroll
           for (int c = 0; c < 4; ++c) v[c] = div_rn(sk[c] + v[c], g.div, rdiv);
         }
-        *reinterpret_cast<f4*>(&y[o]) = v;
-        if (stats) {  // strip st = 4 h + rg joins the st strips (4 st values) before it
-          const float sm = ((v[0] + v[1]) + (v[2] + v[3])) * 0.25f;
-          float sm2 = 0.f;
+#ifdef WINO_F24_EPI_ONE_STORE
+        vsum += v;
+#else
+        *reinterpret_cast<f4*>(&y[obase + r * plane + (int64_t)h * g.W]) = v;
+#endif
+        if (stats) {
+          const float m = ((v[0] + v[1]) + (v[2] + v[3])) * 0.25f;
+          float q = 0.f;
 #pragma unroll
-          for (int c = 0; c < 4; ++c) sm2 = fmaf(v[c] - sm, v[c] - sm, sm2);
-          constexpr float kW[8] = {1.f, 1.f / 2, 1.f / 3, 1.f / 4, 1.f / 5, 1.f / 6, 1.f / 7, 1.f / 8};
-          const int st = 4 * h + rg;
-          const float dd = sm - lm;
-          lm = lm + dd * kW[st];
-          lm2 = (lm2 + sm2) + dd * dd * (4.f * st * kW[st]);
+          for (int c = 0; c < 4; ++c) q = fmaf(v[c] - m, v[c] - m, q);
+          sm[h][r] = m, sm2[h][r] = q;
         }
       }
     }
+#ifdef WINO_F24_EPI_ONE_STORE
+    *reinterpret_cast<f4*>(&y[obase]) = vsum;
+#endif
     WINO_TS_AT(b, 4);
     if (stats) {
-      merge_stats(lm, lm2, __shfl_xor(lm, 16, 64), __shfl_xor(lm2, 16, 64), 32.f);
-      merge_stats(lm, lm2, __shfl_xor(lm, 32, 64), __shfl_xor(lm2, 32, 64), 64.f);
-      if (kq == 0) {
+      // The eight strips of one cout and tile row sit in the quad's four lanes (ttx) x two h.
+      // A 4 x 4 exchange inside the quad gives lane ttx the strips of cout co0 + ttx (sm[h][s]:
+      // the strip of lane s), which it chains in the order st = 4 h + s (strip st joins the
+      // 4 st values before it) -- the merge order of k16_item, so the records keep their bits.
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        quad_transpose(sm[h], ttx);
+        quad_transpose(sm2[h], ttx);
+      }
+      constexpr float kW[8] = {1.f, 1.f / 2, 1.f / 3, 1.f / 4, 1.f / 5, 1.f / 6, 1.f / 7, 1.f / 8};
+      float lm = 0.f, lm2 = 0.f;
+#pragma unroll
+      for (int st = 0; st < 8; ++st) {
+        const float dd = sm[st >> 2][st & 3] - lm;
+        lm = lm + dd * kW[st];
+        lm2 = (lm2 + sm2[st >> 2][st & 3]) + dd * dd * (4.f * st * kW[st]);
+      }
+      // tile rows (0, 1), (2, 3), then the halves
+      merge_stats(lm, lm2, __shfl_xor(lm, 4, 64), __shfl_xor(lm2, 4, 64), 32.f);
+      merge_stats(lm, lm2, __shfl_xor(lm, 8, 64), __shfl_xor(lm2, 8, 64), 64.f);
+      if (tty == 0) {
         const int R = g.regions_x * g.regions_y;
         const int region = (oy0 / kOutRows) * g.regions_x + ox0 / kOutCols;
-        stats[((int64_t)n * g.CoutS + co) * R + region] = make_float2(lm, lm2);
+        stats[((int64_t)n * g.CoutS + co0 + ttx) * R + region] = make_float2(lm, lm2);
       }
     }
   }

@@ -6,8 +6,10 @@ records the 100 MHz wall clock at entry, after its prologue, after its chunk loo
 its epilogue, plus the CU it ran on) and runs the PRE+stats conv of the given shapes.
 Reports per-workgroup phase durations and, per CU, the idle gap between one workgroup's
 end and the next one's start, and how many workgroups were resident on a CU at once.
-Usage: python tools/wino_timing.py [--f24] [cin cout hw] ...  (default: the 128->128@128 and
-256->256@128 shapes of the NCSN++ mix, B=64)
+Usage: python tools/wino_timing.py [--f24] [--skip] [cin cout hw] ...  (default: the
+128->128@128 and 256->256@128 shapes of the NCSN++ mix, B=64)
+
+--skip: with the residual tail, y = (skip + conv) / sqrt 2 (the epilogue's skip loads).
 
 --f24: the F(2x4,3x3) form (wino_f24_k16_kernel, k16_item24).  Its marks are per item, not per
 workgroup -- entry, first V ready, loop start, loop end, stores issued, item end -- so the
@@ -27,7 +29,8 @@ LIB = os.environ.get("WINO_TIMING_LIB", os.path.join(REPO, "b-pinn-kalman-filter
 TICK_US = 0.01  # wall_clock64: 100 MHz
 
 
-def run(lib, B, cin, cout, hw, dev, f24=False):
+def run(lib, B, cin, cout, hw, dev, f24=False, skip=False):
+    P = ctypes.c_void_p
     g = torch.Generator(device=dev).manual_seed(0)
     x = torch.randn(B, cin, hw, hw, device=dev, generator=g)
     w = torch.randn(cout, cin, 3, 3, device=dev, generator=g) / (3 * cin ** 0.5)
@@ -38,9 +41,10 @@ def run(lib, B, cin, cout, hw, dev, f24=False):
         cin, cout) // 4
     U = torch.empty(nU, device=dev)
     y = torch.empty(B, cout, hw, hw, device=dev)
+    sk = torch.randn(B, cout, hw, hw, device=dev, generator=g) if skip else None
+    skp, div = (P(sk.data_ptr()), 2 ** 0.5) if skip else (None, 1.0)
     R = (hw // 8) * (hw // 16)
     part = torch.empty(B, cout, R, 2, device=dev)
-    P = ctypes.c_void_p
     filt = lib.bpk_conv3x3_wino_filter24_f32 if f24 else lib.bpk_conv3x3_wino_filter_f32
     assert filt(P(w.data_ptr()), P(U.data_ptr()), cin, cout, None) == 0
     if f24:
@@ -50,12 +54,12 @@ def run(lib, B, cin, cout, hw, dev, f24=False):
         if f24:
             rc = lib.bpk_conv3x3_wino_f24_splitk_f32(
                 P(x.data_ptr()), None, cin, P(pre.data_ptr()), P(U.data_ptr()), P(b.data_ptr()),
-                None, ctypes.c_float(1.0), P(y.data_ptr()), P(part.data_ptr()), None, B, cin, cout,
+                skp, ctypes.c_float(div), P(y.data_ptr()), P(part.data_ptr()), None, B, cin, cout,
                 hw, hw, None)
         else:
             rc = lib.bpk_conv3x3_wino_ex_f32(P(x.data_ptr()), None, cin, P(pre.data_ptr()),
-                                             P(U.data_ptr()), P(b.data_ptr()), None,
-                                             ctypes.c_float(1.0), P(y.data_ptr()),
+                                             P(U.data_ptr()), P(b.data_ptr()), skp,
+                                             ctypes.c_float(div), P(y.data_ptr()),
                                              P(part.data_ptr()), B, cin, cout, hw, hw, None)
         assert rc == 0, lib.bpk_last_error()
     for _ in range(int(os.environ.get("WINO_TIMING_WARM", "30"))):  # clocks ramp up
@@ -88,7 +92,8 @@ def run(lib, B, cin, cout, hw, dev, f24=False):
     pro, loop, epi = t[:, 1] - t[:, 0], t[:, 2] - t[:, 1], t[:, 3] - t[:, 2]
     span = t[:, 3].max()
     fl = 2.0 * B * cin * cout * 16 * (hw // 2) ** 2
-    print(f"== {cin}->{cout}@{hw} B={B}: {nblk} workgroups, event {ms:.3f} ms, "
+    tail = " + residual tail" if skip else ""
+    print(f"== {cin}->{cout}@{hw} B={B}{tail}: {nblk} workgroups, event {ms:.3f} ms, "
           f"timeline span {span / 1e3:.3f} ms, {fl / ms / 1e9:.1f} TFLOP/s executed; shader clock "
           f"{np.median(ghz):.3f} GHz (p10 {np.percentile(ghz, 10):.3f}, p90 {np.percentile(ghz, 90):.3f})")
     for name, v in (("prologue", pro), ("loop", loop), ("epilogue", epi), ("total", t[:, 3] - t[:, 0])):
@@ -138,12 +143,12 @@ def main():
     lib.bpk_conv3x3_wino_filter24_bytes.restype = ctypes.c_int64
     lib.bpk_conv3x3_wino_splitk_bytes.restype = ctypes.c_int64
     lib.bpk_last_error.restype = ctypes.c_char_p
-    f24 = "--f24" in sys.argv[1:]
-    a = [int(v) for v in sys.argv[1:] if v != "--f24"]
+    f24, skip = "--f24" in sys.argv[1:], "--skip" in sys.argv[1:]
+    a = [int(v) for v in sys.argv[1:] if not v.startswith("--")]
     shapes = [tuple(a[i:i + 3]) for i in range(0, len(a), 3)] or [(128, 128, 128), (256, 256, 128),
                                                                   (256, 256, 32)]
     for cin, cout, hw in shapes:
-        run(lib, 64, cin, cout, hw, dev, f24)
+        run(lib, 64, cin, cout, hw, dev, f24, skip)
 
 
 if __name__ == "__main__":
