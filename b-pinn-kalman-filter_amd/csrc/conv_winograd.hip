@@ -959,6 +959,16 @@ struct Item24Carry {
   bool u_ready;
 };
 
+// Timing diagnostic only (wrong results; tools/build_wino_timing.sh NAME
+// -DWINO_F24_NO_SIDE_WORK=7): the chunk loop without its side work -- bit 0 the data transform
+// (read_d, write_v), bit 1 the patch stores with the SiLU, bit 2 the patch loads.  Every MFMA,
+// filter refill, V operand read, barrier, address and bound stays as it is, so the loop time of
+// such a build is the floor that any placement of that work can reach
+// (profiles/wino_interleave/README.md, section 2).
+#ifndef WINO_F24_NO_SIDE_WORK
+#define WINO_F24_NO_SIDE_WORK 0
+#endif
+
 template <bool PRE, bool TAILK>
 __device__ __forceinline__ void k16_item24(
     unsigned b, unsigned nb, const float* __restrict__ x, const float* __restrict__ U,
@@ -1060,11 +1070,11 @@ __device__ __forceinline__ void k16_item24(
   // at [cin][cout_w / 16][q][jj] (wino_filter24_kernel): 256 contiguous bytes per kq
   f4(&uo)[2][6] = carry.uo;
   const int uoff = ((kq * g.Cout + cout_w) * 24 + jj * 4) * 4;
+  // (wave-uniform by construction; said so, or the tail steps wrap every refill in an exec loop)
   auto u_soff = [&](int k, int ks) {
-    return (((kb + min(k, nch - 1)) * CK + 4 * ks) * g.Cout) * 96;
+    return __builtin_amdgcn_readfirstlane((kb + min(k, nch - 1)) * 4 + ks) * (g.Cout * 384);
   };
-  const int u_soff0[2] = {__builtin_amdgcn_readfirstlane(u_soff(0, 0)),
-                          __builtin_amdgcn_readfirstlane(u_soff(0, 1))};
+  const int u_soff0[2] = {u_soff(0, 0), u_soff(0, 1)};
   auto load_u = [&](int slot, int k, int ks) {
     const int soff = u_soff(k, ks);
 #pragma unroll
@@ -1168,13 +1178,20 @@ __device__ __forceinline__ void k16_item24(
 #pragma unroll
     for (int grp = 0; grp < 8; ++grp) {  // 12 MFMAs each: k-step grp / 2, points 12 (grp & 1) ..
       const int ks = grp >> 1, hf = grp & 1;
+      // side work of the next chunks, fenced off from the MFMAs.  (Issued among the MFMAs --
+      // one MFMA, then four or five vector instructions, by sched_group_barrier -- the loop
+      // measured 3 % slower in this one-workgroup form too.  Its time is the MFMAs' cycles plus
+      // the side work's issue cycles of both waves of a SIMD wherever that work stands:
+      // profiles/wino_interleave/README.md, sections 2 and 3)
       __builtin_amdgcn_sched_barrier(0);
-      if (grp == 0 && TL < 3) read_d(s_patch_raw[SB ^ 1]);                        // patch(k+1)
-      if (grp == 1 && TL < 3) write_v(s_v[SB ^ 1]);                               // V(k+1)
-      if (grp == 2 && TL < 2) store_patch_part(pv, s_patch_raw[SB], k + 2, 0, 4);  // patch(k+2)
-      if (grp == 3 && TL < 2) store_patch_part(pv, s_patch_raw[SB], k + 2, 4, 4);
-      if (grp == 4 && TL < 1) load_patch_part(pv, k + 3, 0, 4);
-      if (grp == 5 && TL < 1) load_patch_part(pv, k + 3, 4, 4);
+      constexpr int kOff = WINO_F24_NO_SIDE_WORK;
+      if (grp == 0 && TL < 3 && !(kOff & 1)) read_d(s_patch_raw[SB ^ 1]);  // patch(k+1)
+      if (grp == 1 && TL < 3 && !(kOff & 1)) write_v(s_v[SB ^ 1]);         // V(k+1)
+      if (grp == 2 && TL < 2 && !(kOff & 2))
+        store_patch_part(pv, s_patch_raw[SB], k + 2, 0, 4);  // patch(k+2)
+      if (grp == 3 && TL < 2 && !(kOff & 2)) store_patch_part(pv, s_patch_raw[SB], k + 2, 4, 4);
+      if (grp == 4 && TL < 1 && !(kOff & 4)) load_patch_part(pv, k + 3, 0, 4);
+      if (grp == 5 && TL < 1 && !(kOff & 4)) load_patch_part(pv, k + 3, 4, 4);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int qq = 0; qq < 3; ++qq) {
