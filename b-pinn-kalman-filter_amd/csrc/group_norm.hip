@@ -6,7 +6,9 @@
 // before GroupNorm_1 (layerspp.py:263-265).
 //
 // NCHW makes every (sample, group) a contiguous slab of S = (C/G)*HW floats, so:
-//  * resident path (S <= 64K floats): one workgroup per slab, the slab is loaded
+//  * resident path (S <= 64K floats on the float4 path; 16K on the scalar path that planes
+//    of no multiple of 4 floats and pointers off 16 bytes take; the backward half of
+//    each): one workgroup per slab, the slab is loaded
 //    ONCE into registers with 16-byte loads, mean and variance are exact two-pass
 //    reductions over the registers, and the normalized output is written once:
 //    1 read + 1 write of HBM per element (the algorithmic minimum).
@@ -654,10 +656,13 @@ struct Plan {
   int chunk;
 };
 
+// resident_max: the last rung of the resident ladder in floats of the W = 4 path.  The ladders
+// count units of W floats, so a scalar (W = 1) slab is resident up to a quarter of it and
+// takes the split path above.
 Plan make_plan(int64_t S, int64_t HW, bool aligned, int64_t resident_max) {
   Plan p{};
   p.W = (HW % 4 == 0 && aligned) ? 4 : 1;
-  p.resident = S <= resident_max;
+  p.resident = S <= resident_max / (4 / p.W);
   p.chunk = kSplitChunk / (4 / p.W);
   p.splits = (int)bpk::ceil_div(S, p.chunk);
   return p;
@@ -790,8 +795,8 @@ extern "C" int bpk_group_norm_bwd_add_f32(const float* dy, const float* x, const
   BPK_REQUIRE(N >= 0 && C > 0 && HW > 0 && G > 0, "group_norm_bwd: bad shape");
   BPK_REQUIRE(C % G == 0, "group_norm_bwd: C (%d) not divisible by G (%d)", C, G);
   BPK_REQUIRE(act == 0 || act == 1, "group_norm_bwd: act must be 0 or 1");
+  if (N == 0) return BPK_OK;  // empty batch: empty tensors have no storage to point at
   BPK_REQUIRE(mean && rstd, "group_norm_bwd: mean/rstd required");
-  if (N == 0) return BPK_OK;
   const int64_t S = (int64_t)(C / G) * HW;
   BPK_REQUIRE(S < (1ll << 31), "group_norm_bwd: slab too large");
   hipStream_t st = bpk::as_stream(stream);
@@ -836,10 +841,11 @@ extern "C" int bpk_group_norm_param_grads_f32(const float* dx, const float* dgam
                                               const float* dbeta_nc, float* d_bias_nc,
                                               float* dgamma, float* dbeta, int N, int C,
                                               int64_t HW, void* stream) {
-  BPK_REQUIRE(N > 0 && C > 0 && HW > 0 && HW < (1ll << 31), "group_norm_param_grads: bad shape");
-  BPK_REQUIRE(!d_bias_nc || dx, "group_norm_param_grads: d_bias_nc needs dx");
-  BPK_REQUIRE(!dgamma || dgamma_nc, "group_norm_param_grads: dgamma needs dgamma_nc");
-  BPK_REQUIRE(!dbeta || dbeta_nc, "group_norm_param_grads: dbeta needs dbeta_nc");
+  BPK_REQUIRE(N >= 0 && C > 0 && HW > 0 && HW < (1ll << 31), "group_norm_param_grads: bad shape");
+  // N = 0: no rows, and dgamma / dbeta are empty sums (zeros) of partials nobody reads
+  BPK_REQUIRE(!d_bias_nc || dx || N == 0, "group_norm_param_grads: d_bias_nc needs dx");
+  BPK_REQUIRE(!dgamma || dgamma_nc || N == 0, "group_norm_param_grads: dgamma needs dgamma_nc");
+  BPK_REQUIRE(!dbeta || dbeta_nc || N == 0, "group_norm_param_grads: dbeta needs dbeta_nc");
   const int rows = d_bias_nc ? N * C : 0;
   const int cols = (dgamma || dbeta) ? (int)bpk::ceil_div(C, 64) : 0;
   if (rows + cols == 0) return BPK_OK;
@@ -857,8 +863,8 @@ extern "C" int bpk_group_norm_affine_stats_f32(const float* x, const float* bias
                                                float eps, void* stream) {
   BPK_REQUIRE(N >= 0 && C > 0 && HW > 0 && G > 0, "group_norm_affine: bad shape");
   BPK_REQUIRE(C % G == 0, "group_norm_affine: C (%d) not divisible by G (%d)", C, G);
-  BPK_REQUIRE(workspace != nullptr, "group_norm_affine: workspace required");
   if (N == 0) return BPK_OK;
+  BPK_REQUIRE(workspace != nullptr, "group_norm_affine: workspace required");
   const int64_t S = (int64_t)(C / G) * HW;
   BPK_REQUIRE(S < (1ll << 31), "group_norm_affine: slab too large");
   hipStream_t st = bpk::as_stream(stream);

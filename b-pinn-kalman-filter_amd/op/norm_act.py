@@ -11,6 +11,8 @@ These are the build's fusions of the NCSN++/DDPM++ block arithmetic
 """
 from __future__ import annotations
 
+import math
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -18,6 +20,11 @@ from torch.autograd.function import once_differentiable
 from ._lib import check, lib, require_hip, stream_ptr, mark_inputs, want_grad
 
 ACT_NONE, ACT_SILU = 0, 1
+
+
+def _plane(x):
+    """H W of x [N, C, ...], from the shape: an empty batch still has its plane."""
+    return math.prod(x.shape[2:])
 
 
 def _ws(N, C, HW, G, device):
@@ -34,7 +41,7 @@ class _GroupNormAct(Function):
             raise RuntimeError(f"group_norm_act: float32 required, got {x.dtype}")
         x = x.contiguous()
         N, C = x.shape[:2]
-        HW = x.numel() // max(N * C, 1)
+        HW = _plane(x)
         y = torch.empty_like(x)
         mean = torch.empty((N, num_groups), device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
@@ -68,7 +75,7 @@ def group_norm_act_backward(dy, x, bnc, weight, bias, mean, rstd, G, act, want_b
     part alone)."""
     dy = dy.contiguous()
     N, C = x.shape[:2]
-    HW = x.numel() // max(N * C, 1)
+    HW = _plane(x)
     dx = torch.empty_like(x)
     need_affine = weight is not None and (want_w or want_b)
     dg = torch.empty((N, C), device=x.device, dtype=torch.float32) if need_affine else None
@@ -193,7 +200,7 @@ def group_norm_affine(x, gn: torch.nn.GroupNorm, bias_nc=None):
         return group_norm_affine_partials(part, x.shape[0], x.shape[1], gn, bias_nc)
     x = x.contiguous()
     N, C = x.shape[:2]
-    HW = x.numel() // max(N * C, 1)
+    HW = _plane(x)
     G = gn.num_groups
     ss = torch.empty((N, C, 2), device=x.device, dtype=torch.float32)
     ws = _ws(N, C, HW, G, x.device)
@@ -219,7 +226,7 @@ def group_norm_affine_stats(x, num_groups, weight, bias, eps, bias_nc=None):
     x = x.contiguous() if gn_partials(x) is None else x
     N, C = x.shape[:2]
     G = num_groups
-    HW = x.numel() // max(N * C, 1)
+    HW = _plane(x)
     ss = torch.empty((N, C, 2), device=x.device, dtype=torch.float32)
     mean = torch.empty((N, G), device=x.device, dtype=torch.float32)
     rstd = torch.empty_like(mean)
