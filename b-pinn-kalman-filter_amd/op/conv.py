@@ -810,110 +810,184 @@ def _fwd_ft_impl(x, w):
     return _fwd_impl(x, _flip_t(w))
 
 
-def _conv_ft_any(x, w):
-    """conv3x3(x, _flip_t(w)) -- the backward-data conv -- recorded for autograd when grad
-    mode is on, else the raw kernels."""
+# ---------------------------------------------------------------- the autograd triple
+# Every differentiable conv of the networks runs through three autograd Functions -- the conv,
+# its adjoint with respect to the input (conv transpose) and the weight gradient -- whose
+# backward passes are written in terms of each other:
+#   d conv / dx = adjoint                   d conv / dw = wgrad(x, gy)
+#   d adjoint / du = conv                   d adjoint / dw = wgrad(gz, u)
+#   d wgrad / dx = adjoint(gy, ggw)         d wgrad / dgy = conv(x, ggw) + ggb
+# Higher derivatives (the PINN residual differentiates the networks twice, create_graph=True)
+# thus stay plain convolutions and weight gradients, instead of the generic convolution double
+# backward, which runs its weight terms as batch/channel-swapped convolutions with H x W
+# kernels (0.5-5 ms each on the PINN shapes).  Which raw kernels run underneath is the `kind`
+# the entry point chose, carried from node to node:
+#   ("3x3",)      3x3 / stride 1 / pad 1: Winograd, small-channel, implicit GEMM, aten (conv3x3)
+#   ("1x1",)      the MFMA GEMMs on the weight [M, K(, 1, 1)] viewed as [M, K] (conv1x1_ad)
+#   ("gen", cfg)  cfg = (stride, padding, dilation, groups): implicit GEMM, aten for what it does
+#                 not take (conv2d_general, conv_transpose2d_general)
+
+def _cfg(ctx_like):
+    return dict(stride=ctx_like[0], padding=ctx_like[1], dilation=ctx_like[2], groups=ctx_like[3])
+
+
+def _w2d(w):
+    return w.reshape(w.shape[0], w.shape[1])
+
+
+def _conv_one(kind, x, w, b=None, skip=None, div=1.0):
+    """conv(x, w) + b without autograd; skip and div (the residual tail) are the 3x3 family's."""
+    if kind[0] == "3x3":
+        return _fwd_impl(x, w, b, skip, div)
+    if kind[0] == "1x1":
+        return _gemm1x1_raw(x, _w2d(w), b)
+    cfg = kind[1]
+    if igemm_supported(x, w, *cfg):
+        return conv2d_igemm_raw(x, w, b, cfg[0], cfg[1])
+    with torch.no_grad():
+        return F.conv2d(x.detach(), w.detach(), None if b is None else b.detach(), **_cfg(cfg))
+
+
+def _convt_one(kind, u, w, xshape):
+    """The adjoint of conv(., w) applied to u (result of shape xshape), without autograd."""
+    if kind[0] == "3x3":
+        return _fwd_ft_impl(u, w)
+    if kind[0] == "1x1":
+        return _gemm1x1_raw(u, _w2d(w).t())  # which makes the transpose contiguous: a copy
+    cfg = kind[1]
+    if (int(cfg[3]) == 1 and _pair(cfg[2]) == (1, 1)
+            and _igemm_ok(u, w.dtype, tuple(int(v) for v in xshape), tuple(w.shape),
+                          _pair(cfg[0]), _pair(cfg[1]))):
+        return conv2d_input_select(xshape, w, u, cfg[0], cfg[1])
+    with torch.no_grad():
+        return torch.nn.grad.conv2d_input(xshape, w.detach(), u.detach(), **_cfg(cfg))
+
+
+def _wgrad_one(kind, wshape, X, GY, want_b):
+    """(dw, db or None) of conv(X, w) for the output gradient GY, without autograd."""
+    if kind[0] == "3x3":
+        return _wgrad_impl(X, GY, wshape, want_b)
+    if kind[0] == "1x1":
+        dw, db = _wgrad1x1_raw(GY, X, bool(want_b))
+        return dw.view(wshape), db
+    cfg = kind[1]
+    if igemm_supported(X, tuple(wshape), *cfg):
+        return conv2d_weight_select(X, wshape, GY, cfg[0], cfg[1], bool(want_b))
+    with torch.no_grad():
+        dw = torch.nn.grad.conv2d_weight(X.detach(), wshape, GY.detach(), **_cfg(cfg))
+        return dw, (GY.detach().sum((0, 2, 3)) if want_b else None)
+
+
+def _conv(x, w, b, kind, skip=None, div=1.0):
+    """_Conv recorded for autograd when grad mode is on (higher derivatives), else the raw
+    kernels."""
     if torch.is_grad_enabled():
-        return _Conv3x3FT.apply(x, w)
-    return _fwd_ft_impl(x, w)
+        return _Conv.apply(x, w, b, skip, div, kind)
+    return _conv_one(kind, x, w, b, skip, div)
 
 
-class _Conv3x3FT(torch.autograd.Function):
-    """y = conv3x3(x, _flip_t(w)) for w [Co, Ci, 3, 3] (x has Co channels).  Adjoint:
-    d/dx = conv3x3(gy, w) (flip_t is an involution); d/dw = _flip_t(wgrad(x, gy)), which is
-    the weight gradient with the roles of input and output gradient exchanged,
-    d/dw[a][b][r][s] = sum_q x[a](q) gy[b](q + (r - 1, s - 1)) = wgrad(gy, x) -- computed in
-    w's own layout (no flip launch, and a contiguous gradient AccumulateGrad can take without
-    a copy).  Both differentiable again (second derivatives of the PINN residual)."""
+def _convt(u, w, xshape, kind):
+    """_ConvT recorded for autograd when grad mode is on, else the raw kernels."""
+    if torch.is_grad_enabled():
+        return _ConvT.apply(u, w, xshape, kind)
+    return _convt_one(kind, u, w, xshape)
+
+
+def _wgrad(x, gy, wshape, want_w, want_b, kind):
+    """(dw if want_w, db if want_b) computed now (not deferred): _Wgrad recorded for autograd
+    when grad mode is on, else the raw kernels."""
+    if not torch.is_grad_enabled():
+        dw, db = _wgrad_one(kind, wshape, x, gy, want_b)
+    elif kind[0] == "3x3":
+        # kept as the 3x3 family had it: under create_graph the node gives dw alone and the
+        # bias gradient is its own sum (the other kinds take both from one kernel)
+        dw = _Wgrad.apply(x, gy, wshape, False, kind)[0] if want_w else None
+        db = gy.sum((0, 2, 3)) if want_b else None
+    else:
+        dw, db = _Wgrad.apply(x, gy, wshape, bool(want_b), kind)
+    return (dw if want_w else None), db
+
+
+class _Conv(torch.autograd.Function):
+    """y = conv(x, w) + b, or for the 3x3 kind with `skip`: (skip + conv(x, w) + b) / div (the
+    other kinds have no skip or div).  Backward: the adjoint and the weight (+ bias) gradient,
+    both differentiable again."""
 
     @staticmethod
-    def forward(ctx, x, w):
-        mark_inputs(ctx, x, w)
+    def forward(ctx, x, w, b, skip, div, kind):
+        mark_inputs(ctx, x, w, b, skip, div, kind)
         ctx.save_for_backward(x, w)
-        return _fwd_ft_impl(x, w)
+        ctx.kind = kind
+        ctx.has_bias = b is not None
+        ctx.bias_leaf = b if b is not None and b.is_leaf else None
+        ctx.div = float(div)
+        return _conv_one(kind, x, w, b, skip, div)
 
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gx = gw = None
-        if want_grad(ctx, 0):
-            gx = _conv_any(gy, w)
-        if want_grad(ctx, 1):
-            if torch.is_grad_enabled():
-                gw = _Wgrad3x3.apply(gy, x, tuple(w.shape))
-            elif not _defer_wgrad(w, gy, x, ("3x3",)):
-                gw = _wgrad_impl(gy, x, tuple(w.shape), False)[0]
-        return gx, gw
-
-
-def _conv_any(x, w):
-    """conv3x3(x, w) recorded for autograd when grad mode is on (higher derivatives), else
-    the raw kernels."""
-    if torch.is_grad_enabled():
-        return _Conv3x3.apply(x, w.contiguous(), None, None, 1.0)
-    return _fwd_impl(x, w)
-
-
-class _Conv3x3(torch.autograd.Function):
-    """y = (skip + conv3x3(x, w) + bias) / div (skip optional).  Its backward is written in
-    terms of this op and _Wgrad3x3, both differentiable again, so second and higher
-    derivatives (the PINN residual, create_graph=True) stay on 3x3 convs and weight
-    gradients -- never on the batch/channel-swapped 'convolutions' with H x W kernels that
-    a generic double backward of a convolution produces."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, skip, div):
-        mark_inputs(ctx, x, weight, bias, skip, div)
-        ctx.save_for_backward(x, weight)
-        ctx.has_bias = bias is not None
-        ctx.bias_leaf = bias if bias is not None and bias.is_leaf else None
-        ctx.div = float(div)
-        return _fwd_impl(x, weight, bias, skip, div)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
         gx = gw = gb = gs = None
         if ctx.div != 1.0:
             gy = gy / ctx.div
         if want_grad(ctx, 3):
             gs = gy
-        want_w, want_b = want_grad(ctx, 1), ctx.has_bias and want_grad(ctx, 2)
         if want_grad(ctx, 0):
-            gx = _conv_ft_any(gy, weight)
-        if torch.is_grad_enabled():
-            if want_w:
-                gw = _Wgrad3x3.apply(x, gy, tuple(weight.shape))
-            if want_b:
-                gb = gy.sum((0, 2, 3))
-        elif _deferred(weight, x, gy, ("3x3",), want_w, want_b, ctx.bias_leaf):
+            gx = _convt(gy, w, tuple(x.shape), ctx.kind)
+        want_w, want_b = want_grad(ctx, 1), ctx.has_bias and want_grad(ctx, 2)
+        if _deferred(w, x, gy, ctx.kind, want_w, want_b, ctx.bias_leaf):
             pass  # weight (and bias) gradients come at the end of the backward pass
         elif want_w or want_b:
-            dw, gb = _wgrad_impl(x, gy, tuple(weight.shape), want_b)
-            gw = dw if want_w else None
-        return gx, gw, gb, gs, None
+            gw, gb = _wgrad(x, gy, tuple(w.shape), want_w, want_b, ctx.kind)
+        return gx, gw, gb, gs, None, None
 
 
-class _Wgrad3x3(torch.autograd.Function):
-    """dw = sum over (n, p) of gy[n, co, p] x[n, ci, p + (r, s)] (the weight gradient of the
-    3x3 / pad-1 conv).  Linear in x and in gy: for an incoming ggw,
-    d/dx = conv3x3(gy, flip_t(ggw)) and d/dgy = conv3x3(x, ggw)."""
+class _ConvT(torch.autograd.Function):
+    """z = A_w^T u, the adjoint of x -> conv(x, w) with respect to its input (shape xshape; for
+    the 3x3 kind conv3x3(u, _flip_t(w)), the Winograd filter transform reading w flipped and
+    transposed in place).  d/du = conv(gz, w); d/dw is the weight gradient with the roles of
+    input and output gradient exchanged, wgrad(gz, u) -- computed in w's own layout (no flip
+    or transposition launch, and a contiguous gradient AccumulateGrad takes without a copy)."""
 
     @staticmethod
-    def forward(ctx, x, gy, wshape):
-        mark_inputs(ctx, x, gy, wshape)
+    def forward(ctx, u, w, xshape, kind):
+        mark_inputs(ctx, u, w, xshape, kind)
+        ctx.save_for_backward(u, w)
+        ctx.kind = kind
+        return _convt_one(kind, u, w, xshape)
+
+    @staticmethod
+    def backward(ctx, gz):
+        u, w = ctx.saved_tensors
+        gu = _conv(gz, w, None, ctx.kind) if want_grad(ctx, 0) else None
+        gw = None
+        if want_grad(ctx, 1) and not _deferred(w, gz, u, ctx.kind, True, False, None):
+            gw = _wgrad(gz, u, tuple(w.shape), True, False, ctx.kind)[0]
+        return gu, gw, None, None
+
+
+class _Wgrad(torch.autograd.Function):
+    """(dw, db or None) = d<conv(x, w) + b, gy>/d(w, b); bilinear in (x, gy): for incoming
+    (ggw, ggb), d/dx = adjoint(gy, ggw) and d/dgy = conv(x, ggw) + ggb."""
+
+    @staticmethod
+    def forward(ctx, x, gy, wshape, bias_grad, kind):
+        mark_inputs(ctx, x, gy, wshape, bias_grad, kind)
         ctx.save_for_backward(x, gy)
-        return _wgrad_impl(x, gy, wshape, False)[0]
+        ctx.kind = kind
+        return _wgrad_one(kind, wshape, x, gy, bias_grad)
 
     @staticmethod
-    def backward(ctx, ggw):
+    def backward(ctx, ggw, ggb):
         x, gy = ctx.saved_tensors
         gx = ggy = None
-        if want_grad(ctx, 0):
-            gx = _conv_ft_any(gy, ggw)
+        if want_grad(ctx, 0) and ggw is not None:
+            gx = _convt(gy, ggw, tuple(x.shape), ctx.kind)
         if want_grad(ctx, 1):
-            ggy = _conv_any(x, ggw)
-        return gx, ggy, None
+            if ggw is not None:
+                ggy = _conv(x, ggw, ggb, ctx.kind)
+            elif ggb is not None:
+                ggy = ggb.view(1, -1, 1, 1).expand_as(gy)
+        return gx, ggy, None, None, None
 
 
 # ---------------------------------------------------------------- deferred weight gradients
@@ -1002,15 +1076,6 @@ def _flush_deferred(d):
                 _accum_grad(b, db)
 
 
-def _wgrad_one(kind, wshape, X, GY, want_b):
-    if kind[0] == "3x3":
-        return _wgrad_impl(X, GY, wshape, want_b)
-    if kind[0] == "1x1":
-        dw, db = _wgrad1x1_raw(GY, X, bool(want_b))
-        return dw.view(wshape), db
-    return _wgrad_fn(X, GY, wshape, kind[1], bool(want_b))
-
-
 def _wgrad_separate(kind, wshape, pairs):
     dw = db = None
     for X, GY, hb in pairs:
@@ -1035,6 +1100,8 @@ def _two_source_ok(kind, wshape, p1, p2):
             return "wino"
         s, p = (1, 1), (1, 1)
     elif kind[0] == "1x1":
+        if len(wshape) != 4:  # a 2-D weight: the implicit GEMM wants [M, K, 1, 1]
+            return None
         s, p = (1, 1), (0, 0)
     else:
         cfg = kind[1]
@@ -1154,7 +1221,7 @@ def conv3x3(x, weight, bias=None, skip=None, div=1.0, pre=None, stats=False):
         return conv3x3_fwd_raw(x, weight, bias, skip, div, pre, stats)
     if stats and wino_supported(x, weight) and not _needs_grad(x, weight, bias, skip):
         return conv3x3_fwd_raw(x, weight, bias, skip, div, None, stats)
-    return _Conv3x3.apply(x, weight, bias, skip, div)
+    return _Conv.apply(x, weight, bias, skip, div, ("3x3",))
 
 
 class _GNSiLUConv3x3(torch.autograd.Function):
@@ -1350,16 +1417,11 @@ class _ConvUp2(torch.autograd.Function):
         x, w = ctx.saved_tensors
         gx = gw = gb = None
         if want_grad(ctx, 0):
-            gx = _sum2x2(_conv_ft_any(gy, w))
-        want_b = ctx.has_bias and want_grad(ctx, 2)
-        if want_grad(ctx, 1) or want_b:
+            gx = _sum2x2(_convt(gy, w, (x.shape[0], x.shape[1]) + tuple(gy.shape[2:]), ("3x3",)))
+        want_w, want_b = want_grad(ctx, 1), ctx.has_bias and want_grad(ctx, 2)
+        if want_w or want_b:
             xu = F.interpolate(x, scale_factor=2, mode="nearest")
-            if torch.is_grad_enabled():
-                gw = _Wgrad3x3.apply(xu, gy, tuple(w.shape)) if want_grad(ctx, 1) else None
-                gb = gy.sum((0, 2, 3)) if want_b else None
-            else:
-                dw, gb = _wgrad_impl(xu, gy, tuple(w.shape), want_b)
-                gw = dw if want_grad(ctx, 1) else None
+            gw, gb = _wgrad(xu, gy, tuple(w.shape), want_w, want_b, ("3x3",))
         return gx, gw, gb
 
 
@@ -1486,230 +1548,27 @@ def _wgrad1x1_raw(gy, x, bias_grad):
     return dw, db
 
 
-def _c1_fn(x, w2d, bias=None):
-    if torch.is_grad_enabled():
-        return _Conv1x1.apply(x, w2d, bias)
-    return _gemm1x1_raw(x, w2d, bias)
-
-
-def _w1_fn(gy, x, bias_grad):
-    if torch.is_grad_enabled():
-        return _Wgrad1x1.apply(gy, x, bias_grad)
-    return _wgrad1x1_raw(gy, x, bias_grad)
-
-
-class _Conv1x1(torch.autograd.Function):
-    """y = w2d @ x[n] + bias.  Backward: the adjoint is the 1x1 conv with w2d^T, the weight
-    and bias gradients one split-K GEMM; all three are differentiable again (PINN residuals
-    take second derivatives through the networks)."""
-
-    @staticmethod
-    def forward(ctx, x, w2d, bias, wref=None):
-        mark_inputs(ctx, x, w2d, bias, wref)
-        ctx.save_for_backward(x, w2d)
-        # the [Cout, Cin, 1, 1] leaf parameter w2d is a view of (deferred weight gradients)
-        ctx.wref = wref
-        ctx.bias_leaf = bias if bias is not None and bias.is_leaf else None
-        return _gemm1x1_raw(x, w2d, bias)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w2d = ctx.saved_tensors
-        gx = None
-        if want_grad(ctx, 0):
-            if ctx.wref is not None and torch.is_grad_enabled():  # the adjoint, still deferrable
-                gx = _Conv1x1.apply(gy, w2d.t(), None, _WRef(ctx.wref.t, not ctx.wref.transposed))
-            else:
-                gx = _c1_fn(gy, w2d.t())
-        gw = gb = None
-        want_w, want_b = want_grad(ctx, 1), want_grad(ctx, 2)
-        # the parameter's gradient from this node: sum gy x^T, or for the adjoint use (w2d is
-        # the parameter transposed) sum x gy^T -- the pair (X, GY) = (gy, x)
-        pair = (gy, x) if ctx.wref is not None and ctx.wref.transposed else (x, gy)
-        if ctx.wref is not None and _deferred(ctx.wref.t, pair[0], pair[1], ("1x1",), want_w,
-                                              want_b, ctx.bias_leaf):
-            pass  # deferred to the end of the backward pass
-        elif want_w or want_b:
-            gw, gb = _w1_fn(gy, x, bool(want_b))
-            if not want_w:
-                gw = None
-        return gx, gw, gb, None
-
-
-class _WRef:
-    """A parameter passed to a Function as a plain reference (no autograd edge); transposed:
-    the Function's weight is the parameter's transpose (the 1x1 conv's adjoint)."""
-    __slots__ = ("t", "transposed")
-
-    def __init__(self, t, transposed=False):
-        self.t = t
-        self.transposed = transposed
-
-
-class _Wgrad1x1(torch.autograd.Function):
-    """(dw, db) = (sum_n gy[n] x[n]^T, gy.sum((0, 2, 3))); bilinear in (gy, x)."""
-
-    @staticmethod
-    def forward(ctx, gy, x, bias_grad):
-        mark_inputs(ctx, gy, x, bias_grad)
-        ctx.save_for_backward(gy, x)
-        return _wgrad1x1_raw(gy, x, bias_grad)
-
-    @staticmethod
-    def backward(ctx, ggw, ggb):
-        gy, x = ctx.saved_tensors
-        g_gy = g_x = None
-        if want_grad(ctx, 0):
-            if ggw is not None:
-                g_gy = _c1_fn(x, ggw, ggb)  # ggw x[n] + ggb
-            elif ggb is not None:
-                g_gy = ggb.view(1, -1, 1, 1).expand_as(gy)
-        if want_grad(ctx, 1) and ggw is not None:
-            g_x = _c1_fn(gy, ggw.t())
-        return g_gy, g_x, None
-
-
 def conv1x1_ad(x, weight, bias=None):
     """1x1 conv with autograd on the GEMM kernels (every derivative order); shapes must pass
     conv1x1_train_supported.  weight [Cout, Cin(, 1, 1)]."""
     require_hip(x, weight, bias, what="conv1x1")
     if not conv1x1_train_supported(x, weight):
         raise RuntimeError(f"conv1x1: unsupported shape {tuple(x.shape)} x {tuple(weight.shape)}")
-    w2d = weight.reshape(weight.shape[0], weight.shape[1])
-    if torch.is_grad_enabled() and weight.is_leaf and weight.dim() == 4:
-        return _Conv1x1.apply(x, w2d, bias, _WRef(weight))
-    return _c1_fn(x, w2d, bias)
+    return _conv(x, weight, bias, ("1x1",))
 
 
 # ---------------------------------------------------------------- general convolutions
-# Every other Conv2d / ConvTranspose2d of the networks (stride-2 3x3, the PINN's tiny
-# levels and odd channel counts, 2x2 / 4x4 transposed convs, ...) runs through three
-# autograd Functions -- conv, its adjoint (conv transpose) and the weight gradient -- whose
-# backward passes are written in terms of each other.  Higher derivatives (the PINN
-# residual differentiates the networks twice) thus stay plain convolutions, instead of the
-# generic convolution double backward, which runs its weight terms as batch/channel-swapped
-# convolutions with H x W kernels (0.5-5 ms each on the PINN shapes).  Underneath: the
-# implicit-GEMM MFMA kernels (igemm_supported), MIOpen for anything else (groups, dilation).
-
-def _cfg(ctx_like):
-    return dict(stride=ctx_like[0], padding=ctx_like[1], dilation=ctx_like[2], groups=ctx_like[3])
-
-
-def _ig_ok(x, w, cfg):
-    return igemm_supported(x, w, cfg[0], cfg[1], cfg[2], cfg[3])
-
-
-def _conv_fn(x, w, cfg, b=None):
-    if torch.is_grad_enabled():
-        return _ConvG.apply(x, w, b, cfg)
-    return _ConvG.forward(None, x, w, b, cfg)
-
-
-def _convt_fn(u, w, xshape, cfg):
-    if torch.is_grad_enabled():
-        return _ConvTG.apply(u, w, xshape, cfg)
-    return _ConvTG.forward(None, u, w, xshape, cfg)
-
-
-def _wgrad_fn(x, gy, wshape, cfg, bias_grad=False):
-    """(dw, db or None)"""
-    if torch.is_grad_enabled():
-        return _WgradG.apply(x, gy, wshape, cfg, bias_grad)
-    return _WgradG.forward(None, x, gy, wshape, cfg, bias_grad)
-
-
-class _ConvG(torch.autograd.Function):
-    """y = conv2d(x, w) + b; grads: conv transpose, weight (+ bias) gradient."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, cfg):
-        mark_inputs(ctx, x, w, b, cfg)
-        if ctx is not None:
-            ctx.save_for_backward(x, w)
-            ctx.cfg = cfg
-            ctx.has_b = b is not None
-            ctx.bias_leaf = b if b is not None and b.is_leaf else None
-        if _ig_ok(x, w, cfg):
-            return conv2d_igemm_raw(x, w, b, cfg[0], cfg[1])
-        with torch.no_grad():
-            return F.conv2d(x.detach(), w.detach(), None if b is None else b.detach(), **_cfg(cfg))
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        gx = _convt_fn(gy, w, tuple(x.shape), ctx.cfg) if want_grad(ctx, 0) else None
-        gw = gb = None
-        want_w, want_b = want_grad(ctx, 1), ctx.has_b and want_grad(ctx, 2)
-        if _deferred(w, x, gy, ("gen", ctx.cfg), want_w, want_b, ctx.bias_leaf):
-            pass  # deferred to the end of the backward pass
-        elif want_w or want_b:
-            gw, gb = _wgrad_fn(x, gy, tuple(w.shape), ctx.cfg, bool(want_b))
-            if not want_w:
-                gw = None
-        return gx, gw, gb, None
-
-
-class _ConvTG(torch.autograd.Function):
-    """z = conv2d's adjoint w.r.t. its input: z = A_w^T u (shape xshape)."""
-
-    @staticmethod
-    def forward(ctx, u, w, xshape, cfg):
-        mark_inputs(ctx, u, w, xshape, cfg)
-        if ctx is not None:
-            ctx.save_for_backward(u, w)
-            ctx.cfg = cfg
-        if (int(cfg[3]) == 1 and _pair(cfg[2]) == (1, 1)
-                and _igemm_ok(u, w.dtype, tuple(int(v) for v in xshape), tuple(w.shape),
-                              _pair(cfg[0]), _pair(cfg[1]))):
-            return conv2d_input_select(xshape, w, u, cfg[0], cfg[1])
-        with torch.no_grad():
-            return torch.nn.grad.conv2d_input(xshape, w.detach(), u.detach(), **_cfg(cfg))
-
-    @staticmethod
-    def backward(ctx, gz):
-        u, w = ctx.saved_tensors
-        gu = _conv_fn(gz, w, ctx.cfg) if want_grad(ctx, 0) else None
-        gw = None
-        if want_grad(ctx, 1) and (torch.is_grad_enabled()
-                                  or not _defer_wgrad(w, gz, u, ("gen", ctx.cfg))):
-            gw = _wgrad_fn(gz, u, tuple(w.shape), ctx.cfg)[0]
-        return gu, gw, None, None
-
-
-class _WgradG(torch.autograd.Function):
-    """(dw, db) = d<conv2d(x, w) + b, gy>/d(w, b); bilinear in (x, gy)."""
-
-    @staticmethod
-    def forward(ctx, x, gy, wshape, cfg, bias_grad):
-        mark_inputs(ctx, x, gy, wshape, cfg, bias_grad)
-        if ctx is not None:
-            ctx.save_for_backward(x, gy)
-            ctx.cfg = cfg
-        if _ig_ok(x, tuple(wshape), cfg):
-            return conv2d_weight_select(x, wshape, gy, cfg[0], cfg[1], bias_grad)
-        with torch.no_grad():
-            dw = torch.nn.grad.conv2d_weight(x.detach(), wshape, gy.detach(), **_cfg(cfg))
-            return dw, (gy.detach().sum((0, 2, 3)) if bias_grad else None)
-
-    @staticmethod
-    def backward(ctx, ggw, ggb):
-        x, gy = ctx.saved_tensors
-        gx = ggy = None
-        if want_grad(ctx, 0) and ggw is not None:
-            gx = _convt_fn(gy, ggw, tuple(x.shape), ctx.cfg)
-        if want_grad(ctx, 1):
-            if ggw is not None:
-                ggy = _conv_fn(x, ggw, ctx.cfg, ggb)
-            elif ggb is not None:
-                ggy = ggb.view(1, -1, 1, 1).expand_as(gy)
-        return gx, ggy, None, None, None
-
+# Every other Conv2d / ConvTranspose2d of the networks (stride-2 3x3, the PINN's tiny levels
+# and odd channel counts, 2x2 / 4x4 transposed convs, ...): the "gen" kind of the autograd
+# triple, on the implicit-GEMM MFMA kernels (igemm_supported), MIOpen for anything else
+# (groups, dilation).
 
 def conv2d_general(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
     """F.conv2d with every derivative order expressed as convolutions / conv transposes /
-    weight gradients (see above); bias fused into the forward and weight-gradient kernels."""
+    weight gradients (the autograd triple); bias fused into the forward and weight-gradient
+    kernels."""
     cfg = (_pair(stride), _pair(padding), _pair(dilation), int(groups))
-    return _conv_fn(x, weight, cfg, bias)
+    return _conv(x, weight, bias, ("gen", cfg))
 
 
 def _dense_groups(w, groups):
@@ -1733,5 +1592,5 @@ def conv_transpose2d_general(u, weight, bias=None, stride=1, padding=0, output_p
     N, _, Hu, Wu = u.shape
     Ho = (Hu - 1) * s[0] - 2 * p[0] + d[0] * (w.shape[2] - 1) + op[0] + 1
     Wo = (Wu - 1) * s[1] - 2 * p[1] + d[1] * (w.shape[3] - 1) + op[1] + 1
-    y = _convt_fn(u, w, (N, w.shape[1], Ho, Wo), (s, p, d, 1))
+    y = _convt(u, w, (N, w.shape[1], Ho, Wo), ("gen", (s, p, d, 1)))
     return y if bias is None else y + bias.view(1, -1, 1, 1)

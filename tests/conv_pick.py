@@ -123,8 +123,8 @@ W2_CASES = [
 ]
 # The candidates each case can run.  The second candidate of the 1x1 kind is the 1x1 GEMM weight
 # gradient (conv._wgrad1x1_raw), which takes channel counts and pixel counts that are multiples
-# of 16 only (bpk_gemm_nchw_wgrad_supported): the autograd node that records ("1x1",) pairs
-# (conv._Conv1x1) runs for no other shape.  33 -> 17 channels at 5 x 5 therefore exists as a
+# of 16 only (bpk_gemm_nchw_wgrad_supported): the autograd nodes that record ("1x1",) pairs
+# (conv._Conv and conv._ConvT of that kind, through conv1x1_ad) run for no other shape.  33 -> 17 channels at 5 x 5 therefore exists as a
 # two-source launch alone, and 48 -> 32 at 4 x 4 is the smallest shape with both candidates.
 W2_CANDIDATES = {"1x1_odd": (0,)}
 # the choice nested under w2 = 1 (_wgrad_separate -> _wgrad_one) per case: a tag, or None

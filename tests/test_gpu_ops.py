@@ -870,6 +870,21 @@ def test_conv1x1_autograd_double_backward(hip, cin, cout, hw):
             continue
         assert (a - r).abs().max().item() <= 2e-5 * max(1e-6, r.abs().max().item())
 
+    # the adjoint node's weight gradient, not deferred (a double backward into .grad outside
+    # deferred_weight_grads): computed in the parameter's own layout, so contiguous; vs float64
+    def pinn(fn, dev, dt):
+        x = x0.to(dev, dt).requires_grad_()
+        w = w0.to(dev, dt).requires_grad_()
+        gx, = torch.autograd.grad(fn(torch.tanh(x), w, b0.to(dev, dt)), x, go.to(dev, dt),
+                                  create_graph=True)
+        (gx * gx).sum().backward()
+        return w.grad
+
+    gw = pinn(conv1x1_ad, hip, torch.float32)
+    gw_ref = pinn(lambda x, w, b: F.conv2d(x, w, b), "cpu", torch.float64)
+    assert gw.is_contiguous() and gw.shape == w0.shape
+    assert (gw.cpu() - gw_ref).abs().max().item() <= 2e-5 * max(1e-6, gw_ref.abs().max().item())
+
 
 def test_conv3x3_winograd_two_sources(hip):
     """The Winograd conv reading [x1, x2] as two sources equals the conv of their
