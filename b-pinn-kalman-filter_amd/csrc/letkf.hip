@@ -1,21 +1,34 @@
-// Local ensemble transform Kalman filter analysis (Hunt, Kostelich & Szunyogh 2007) with an
-// identity observation of the state, float32 (include/bpk.h, section "letkf").  Two launches:
+// Local ensemble transform Kalman filter analysis (Hunt, Kostelich & Szunyogh 2007), float32
+// (include/bpk.h, section "letkf"), in two entries that share one kernel body: the identity
+// observation of the state (bpk_letkf_analysis_f32: the observation-space perturbations dY are
+// the state's own dX), and observations on a grid of their own behind any operator
+// (bpk_letkf_analysis_obs_f32: the caller passes the members in observation space, yens
+// [B, m, Cy, Hy, Wy], and observation (i, j) sits at state grid point (stride i + offset,
+// stride j + offset)).  Two launches for the identity, three with yens:
 //
 //   k_letkf_prep  member mean xbar [B, C, H, W] and the perturbations dX = ens - xbar written
 //                 member-innermost, dxt [B, H, W, C, MP] (MP = m padded to 8 / 16 / 32 / 64, the
 //                 pad members hold 0), into the workspace.  Reads are coalesced on x; the
 //                 analysis kernel then reads one window entry of all members as one contiguous
-//                 run of MP floats, and the C entries of a site are adjacent.
-//   k_letkf<MP>   one 64-thread block (one wave) per 64 / MP grid points: lane = (g, r), group g
+//                 run of MP floats, and the C entries of a site are adjacent.  Run a second
+//                 time on yens for ybar and dyt [B, Hy, Wy, Cy, MP].
+//   k_letkf<MP, OBS>
+//                 one 64-thread block (one wave) per 64 / MP grid points: lane = (g, r), group g
 //                 works on grid point blockIdx * G + g, r is the member.
-//                   1. A = (m-1)/inflation I + sum_j rho_j dX_j dX_j^T and g = sum_j rho_j dX_j
-//                      (obs_j - xbar_j): lane r keeps row r of A in MP registers; the other
-//                      members' dX_j come from a double-buffered LDS row (one barrier per
+//                   1. A = (m-1)/inflation I + sum_j rho_j dY_j dY_j^T and g = sum_j rho_j dY_j
+//                      (obs_j - ybar_j): lane r keeps row r of A in MP registers; the other
+//                      members' dY_j come from a double-buffered LDS row (one barrier per
 //                      entry, 16-byte reads).  The window is walked in the fixed order
-//                      (dy, dx, c) over the whole (2R+1)^2 C box with wave-uniform bounds;
+//                      (dy, dx, c) over the whole (2R+1)^2 Cy box with wave-uniform bounds;
 //                      clipped, tapered-out and unobserved entries are predicated off, and an
-//                      entry no lane of the wave needs is skipped as a whole.  (dX_r dX_k) rho is
-//                      rounded in that order, so A is symmetric bit for bit.
+//                      entry no lane of the wave needs is skipped as a whole.  Whether a window
+//                      position carries an observation ((y - offset) % stride == 0) and which
+//                      one are running per-lane counters, one division before the loops, and
+//                      rows and positions between the observations are skipped whole where the
+//                      wave agrees.  The identity instantiation (OBS = false) has none of this:
+//                      it indexes the state's grid directly, (y0 + dy, x0 + dx).
+//                      (dY_r dY_k) rho is rounded in that order, so A is symmetric bit for bit,
+//                      and with yens == ens, stride 1 the two entries give the same bits.
 //                   2. Two-sided cyclic Jacobi on A and Q (= I at the start) in LDS tiles of row
 //                      stride MP + 1 (as the [64][65] tiles of ukf.hip: row and column walks are
 //                      both conflict free).  A sweep is MP - 1 rounds of the round-robin
@@ -91,12 +104,25 @@ __device__ __forceinline__ void rr_pair(int t, int i, int& p, int& q) {
   q = a < b ? b : a;
 }
 
-template <int MP>
+// observation grid: observation (i, j) of [Cy, Hy, Wy] sits at state point (stride i + offset,
+// stride j + offset); ybar / dyt are the prep kernel's output for the observation-space members
+struct ObsGrid {
+  const float* ybar;
+  const float* dyt;
+  int Cy, Hy, Wy, stride, offset;
+};
+
+// floor(a / s) for s >= 1
+__device__ __forceinline__ int floor_div(int a, int s) { return a >= 0 ? a / s : -((s - 1 - a) / s); }
+
+// OBS = false: the identity observation (dY = dX on the state's grid); og is not read, and
+// that path pays nothing for the observation grid's indexing
+template <int MP, bool OBS>
 __global__ __launch_bounds__(kWave) void k_letkf(
     const float* __restrict__ xbar, const float* __restrict__ dxt, const float* __restrict__ obs,
     const float* __restrict__ prec, const float* __restrict__ taper, float* __restrict__ ens_out,
     int* __restrict__ status, int64_t N, int m, int C, int H, int W, int R, float a0,
-    float sqrt_m1, float sqrt_infl) {
+    float sqrt_m1, float sqrt_infl, const ObsGrid og) {
   constexpr int G = kWave / MP, LD = MP + 1, HP = MP / 2;
   __shared__ float As[G * MP * LD];
   __shared__ float Qs[G * MP * LD];
@@ -121,21 +147,60 @@ __global__ __launch_bounds__(kWave) void k_letkf(
   for (int k = 0; k < MP; ++k) acc[k] = 0.f;
   float gacc = 0.f;
   const int win = 2 * R + 1;
+  // the identity observes the state's own grid: dY is dX, every window position carries an
+  // observation, and stride, offset and the counters below are unused (dead code)
+  const float* __restrict__ ybar = OBS ? og.ybar : xbar;
+  const float* __restrict__ dyt = OBS ? og.dyt : dxt;
+  const int Cy = OBS ? og.Cy : C, Hy = OBS ? og.Hy : H, Wy = OBS ? og.Wy : W;
+  const int stride = OBS ? og.stride : 1, offset = OBS ? og.offset : 0;
+  const int64_t HWy = (int64_t)Hy * Wy;
+  // window position y0 + dy = stride * iy + offset + ry, 0 <= ry < stride, kept while dy runs
+  // (likewise x): it carries observation row iy where ry == 0 and 0 <= iy < Hy, which lies
+  // inside the state's domain because stride (Hy - 1) + offset <= H - 1
+  const int iy_first = floor_div(y0 - R - offset, stride);
+  const int ix_first = floor_div(x0 - R - offset, stride);
+  const int ry_first = y0 - R - offset - iy_first * stride;
+  const int rx_first = x0 - R - offset - ix_first * stride;
   int e = 0;
-  for (int dy = -R; dy <= R; ++dy) {
-    for (int dx = -R; dx <= R; ++dx) {
+  int iy = iy_first, ry = ry_first;
+  for (int dy = -R; dy <= R; ++dy, ++ry) {
+    bool hit_y = active;
+    if constexpr (OBS) {
+      if (ry == stride) {
+        ry = 0;
+        ++iy;
+      }
+      hit_y = active && ry == 0 && iy >= 0 && iy < Hy;
+      if (!__any(hit_y)) continue;  // wave-uniform: a row between the observations' rows
+    }
+    int ix = ix_first, rx = rx_first;
+    for (int dx = -R; dx <= R; ++dx, ++rx) {
+      if constexpr (OBS) {
+        if (rx == stride) {
+          rx = 0;
+          ++ix;
+        }
+      }
       const float tp = taper[(dy + R) * win + dx + R];
       if (tp == 0.f) continue;  // wave-uniform
-      const int y = y0 + dy, x = x0 + dx;
-      const bool inwin = active && y >= 0 && y < H && x >= 0 && x < W;
-      for (int c = 0; c < C; ++c) {
+      int y, x;  // the entry's row and column on the observation grid
+      bool inwin;
+      if constexpr (OBS) {
+        y = iy, x = ix;
+        inwin = hit_y && rx == 0 && ix >= 0 && ix < Wy;
+        if (!__any(inwin)) continue;  // wave-uniform: no observation sits here
+      } else {
+        y = y0 + dy, x = x0 + dx;
+        inwin = active && y >= 0 && y < H && x >= 0 && x < W;
+      }
+      for (int c = 0; c < Cy; ++c) {
         float rho = 0.f, dv = 0.f, innov = 0.f;
         if (inwin) {
-          const int64_t idx = ((b * C + c) * H + y) * W + x;
+          const int64_t idx = ((b * Cy + c) * Hy + y) * Wy + x;
           rho = tp * prec[idx];
           if (rho != 0.f) {
-            dv = dxt[((b * HW + (int64_t)y * W + x) * C + c) * MP + r];
-            innov = obs[idx] - xbar[idx];
+            dv = dyt[((b * HWy + (int64_t)y * Wy + x) * Cy + c) * MP + r];
+            innov = obs[idx] - ybar[idx];
           }
         }
         if (!__any(rho != 0.f)) continue;  // wave-uniform: nobody observes this entry
@@ -282,14 +347,41 @@ __global__ __launch_bounds__(kWave) void k_letkf(
   }
 }
 
+// og == nullptr: the identity observation
 template <int MP>
-void launch(const float* xbar, const float* dxt, const float* obs, const float* prec,
-            const float* taper, float* ens_out, int* status, int64_t N, int m, int C, int H, int W,
-            int R, float inflation, hipStream_t stream) {
+void launch(const float* xbar, const float* dxt, const ObsGrid* og, const float* obs,
+            const float* prec, const float* taper, float* ens_out, int* status, int64_t N, int m,
+            int C, int H, int W, int R, float inflation, hipStream_t stream) {
   constexpr int G = kWave / MP;
-  hipLaunchKernelGGL(k_letkf<MP>, dim3((unsigned)((N + G - 1) / G)), dim3(kWave), 0, stream, xbar,
-                     dxt, obs, prec, taper, ens_out, status, N, m, C, H, W, R,
-                     (float)(m - 1) / inflation, sqrtf((float)(m - 1)), sqrtf(inflation));
+  const dim3 grid((unsigned)((N + G - 1) / G));
+  const float a0 = (float)(m - 1) / inflation, sqrt_m1 = sqrtf((float)(m - 1));
+  if (og == nullptr)
+    hipLaunchKernelGGL((k_letkf<MP, false>), grid, dim3(kWave), 0, stream, xbar, dxt, obs, prec,
+                       taper, ens_out, status, N, m, C, H, W, R, a0, sqrt_m1, sqrtf(inflation),
+                       ObsGrid{});
+  else
+    hipLaunchKernelGGL((k_letkf<MP, true>), grid, dim3(kWave), 0, stream, xbar, dxt, obs, prec,
+                       taper, ens_out, status, N, m, C, H, W, R, a0, sqrt_m1, sqrtf(inflation),
+                       *og);
+}
+
+void launch_padded(int MP, const float* xbar, const float* dxt, const ObsGrid* og,
+                   const float* obs, const float* prec, const float* taper, float* ens_out,
+                   int* status, int64_t N, int m, int C, int H, int W, int R, float inflation,
+                   hipStream_t s) {
+  switch (MP) {
+    case 8: launch<8>(xbar, dxt, og, obs, prec, taper, ens_out, status, N, m, C, H, W, R, inflation, s); break;
+    case 16: launch<16>(xbar, dxt, og, obs, prec, taper, ens_out, status, N, m, C, H, W, R, inflation, s); break;
+    case 32: launch<32>(xbar, dxt, og, obs, prec, taper, ens_out, status, N, m, C, H, W, R, inflation, s); break;
+    default: launch<64>(xbar, dxt, og, obs, prec, taper, ens_out, status, N, m, C, H, W, R, inflation, s); break;
+  }
+}
+
+void launch_prep(const float* ens, float* mean, float* pert, int64_t B, int m, int C, int64_t HW,
+                 int MP, hipStream_t s) {
+  const int64_t total = B * HW * C;
+  hipLaunchKernelGGL(k_letkf_prep, dim3((unsigned)bpk::ceil_div(total, 256)), dim3(256), 0, s, ens,
+                     mean, pert, total, m, C, HW, MP);
 }
 
 bool geometry_ok(int64_t B, int m, int C, int H, int W) {
@@ -333,15 +425,79 @@ extern "C" int bpk_letkf_analysis_f32(const float* ens, const float* obs, const 
   float* xbar = static_cast<float*>(workspace);
   float* dxt = xbar + total;
   hipStream_t s = bpk::as_stream(stream);
-  hipLaunchKernelGGL(k_letkf_prep, dim3((unsigned)bpk::ceil_div(total, 256)), dim3(256), 0, s, ens,
-                     xbar, dxt, total, m, C, HW, MP);
+  launch_prep(ens, xbar, dxt, B, m, C, HW, MP, s);
   BPK_LAUNCH_CHECK("letkf_analysis (prep)");
-  switch (MP) {
-    case 8: launch<8>(xbar, dxt, obs, prec, taper, ens_out, status, N, m, C, H, W, R, inflation, s); break;
-    case 16: launch<16>(xbar, dxt, obs, prec, taper, ens_out, status, N, m, C, H, W, R, inflation, s); break;
-    case 32: launch<32>(xbar, dxt, obs, prec, taper, ens_out, status, N, m, C, H, W, R, inflation, s); break;
-    default: launch<64>(xbar, dxt, obs, prec, taper, ens_out, status, N, m, C, H, W, R, inflation, s); break;
-  }
+  launch_padded(MP, xbar, dxt, nullptr, obs, prec, taper, ens_out, status, N, m, C, H, W, R,
+                inflation, s);
   BPK_LAUNCH_CHECK("letkf_analysis");
+  return BPK_OK;
+}
+
+extern "C" int64_t bpk_letkf_obs_workspace_bytes(int64_t B, int m, int C, int H, int W, int Cy,
+                                                 int Hy, int Wy) {
+  if (!geometry_ok(B, m, C, H, W) || !geometry_ok(B, m, Cy, Hy, Wy)) return -1;
+  return (B * C * H * W + B * Cy * Hy * Wy) * (int64_t)(1 + padded_members(m)) *
+         (int64_t)sizeof(float);
+}
+
+extern "C" int bpk_letkf_analysis_obs_f32(const float* ens, const float* yens, const float* obs,
+                                          const float* prec, const float* taper, float* ens_out,
+                                          int* status, void* workspace, int64_t B, int m, int C,
+                                          int H, int W, int Cy, int Hy, int Wy, int stride,
+                                          int offset, int R, float inflation, void* stream) {
+  BPK_REQUIRE(m >= 2 && m <= kMaxM, "letkf_analysis_obs: m = %d out of range [2, %d]", m, kMaxM);
+  BPK_REQUIRE(C >= 1 && C <= kMaxC, "letkf_analysis_obs: C = %d out of range [1, %d]", C, kMaxC);
+  BPK_REQUIRE(Cy >= 1 && Cy <= kMaxC, "letkf_analysis_obs: Cy = %d out of range [1, %d]", Cy,
+              kMaxC);
+  BPK_REQUIRE(R >= 0 && R <= kMaxR, "letkf_analysis_obs: R = %d out of range [0, %d]", R, kMaxR);
+  BPK_REQUIRE(H >= 1, "letkf_analysis_obs: H = %d must be >= 1", H);
+  BPK_REQUIRE(W >= 1, "letkf_analysis_obs: W = %d must be >= 1", W);
+  BPK_REQUIRE(Hy >= 1, "letkf_analysis_obs: Hy = %d must be >= 1", Hy);
+  BPK_REQUIRE(Wy >= 1, "letkf_analysis_obs: Wy = %d must be >= 1", Wy);
+  BPK_REQUIRE(stride >= 1, "letkf_analysis_obs: stride = %d must be >= 1", stride);
+  BPK_REQUIRE(offset >= 0 && offset < stride,
+              "letkf_analysis_obs: offset = %d out of range [0, stride = %d)", offset, stride);
+  BPK_REQUIRE((int64_t)stride * (Hy - 1) + offset <= (int64_t)H - 1,
+              "letkf_analysis_obs: Hy = %d does not fit: stride * (Hy - 1) + offset = %lld > "
+              "H - 1 = %d",
+              Hy, (long long)((int64_t)stride * (Hy - 1) + offset), H - 1);
+  BPK_REQUIRE((int64_t)stride * (Wy - 1) + offset <= (int64_t)W - 1,
+              "letkf_analysis_obs: Wy = %d does not fit: stride * (Wy - 1) + offset = %lld > "
+              "W - 1 = %d",
+              Wy, (long long)((int64_t)stride * (Wy - 1) + offset), W - 1);
+  BPK_REQUIRE(inflation > 0.f && inflation <= FLT_MAX,
+              "letkf_analysis_obs: inflation = %g must be positive and finite", (double)inflation);
+  BPK_REQUIRE(geometry_ok(B, m, C, H, W) && geometry_ok(B, m, Cy, Hy, Wy),
+              "letkf_analysis_obs: B = %lld out of range (B H W and B Hy Wy < 2^31)",
+              (long long)B);
+  BPK_REQUIRE(ens_out == nullptr || ens_out != ens,
+              "letkf_analysis_obs: ens_out must not alias ens (neighbours read the background)");
+  BPK_REQUIRE(ens_out == nullptr || ens_out != yens,
+              "letkf_analysis_obs: ens_out must not alias yens (neighbours read it)");
+  if (B == 0) return BPK_OK;
+  BPK_REQUIRE(ens != nullptr, "letkf_analysis_obs: ens is NULL");
+  BPK_REQUIRE(yens != nullptr, "letkf_analysis_obs: yens is NULL");
+  BPK_REQUIRE(obs != nullptr, "letkf_analysis_obs: obs is NULL");
+  BPK_REQUIRE(prec != nullptr, "letkf_analysis_obs: prec is NULL");
+  BPK_REQUIRE(taper != nullptr, "letkf_analysis_obs: taper is NULL");
+  BPK_REQUIRE(ens_out != nullptr, "letkf_analysis_obs: ens_out is NULL");
+  BPK_REQUIRE(status != nullptr, "letkf_analysis_obs: status is NULL");
+  BPK_REQUIRE(workspace != nullptr, "letkf_analysis_obs: workspace is NULL");
+
+  const int MP = padded_members(m);
+  const int64_t HW = (int64_t)H * W, N = B * HW, HWy = (int64_t)Hy * Wy;
+  float* xbar = static_cast<float*>(workspace);
+  float* dxt = xbar + N * C;
+  float* ybar = dxt + N * C * MP;
+  float* dyt = ybar + B * HWy * Cy;
+  hipStream_t s = bpk::as_stream(stream);
+  launch_prep(ens, xbar, dxt, B, m, C, HW, MP, s);
+  BPK_LAUNCH_CHECK("letkf_analysis_obs (prep of ens)");
+  launch_prep(yens, ybar, dyt, B, m, Cy, HWy, MP, s);
+  BPK_LAUNCH_CHECK("letkf_analysis_obs (prep of yens)");
+  const ObsGrid og{ybar, dyt, Cy, Hy, Wy, stride, offset};
+  launch_padded(MP, xbar, dxt, &og, obs, prec, taper, ens_out, status, N, m, C, H, W, R, inflation,
+                s);
+  BPK_LAUNCH_CHECK("letkf_analysis_obs");
   return BPK_OK;
 }

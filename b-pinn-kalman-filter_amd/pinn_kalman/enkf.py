@@ -12,8 +12,15 @@ B * m simulator replicas that differ.  One filter step is
 Next to the patch UKF (129 simulator steps per filter step, no covariance across a patch
 border) this costs m simulator steps per frame, its covariances are the flow's own and cross
 any border, and unlike `FourDVar` it is sequential and returns a spread next to the mean.
-The observation is the masked identity: `weights` are the inverse variances of
+By default the observation is the masked identity: `weights` are the inverse variances of
 `fourdvar.observation_weights` (0 = unobserved).
+
+With `observe` the filter assimilates observations on a grid of their own behind any operator
+the members can be passed through, e.g. `blur_observation`: a blurred, low-resolution image of
+some channels (`op.letkf.analysis_obs`).  An observation is localized at its sampling point
+(`obs_stride * i + obs_offset`), so the operator's footprint (K // 2 for a K-tap blur) should
+be small against the radius R.  With a window that sees every observation at full weight the
+analysis is the exact Kalman update for any linear operator.
 
 Everything stays on the device: `filter` never reads a value on the host, and the number of
 grid points the analysis flagged is summed per frame into a device tensor.
@@ -45,6 +52,21 @@ class EnsembleHistory:
         return self.means.shape[0]
 
 
+def blur_observation(taps, stride=1, channels=None):
+    """The observation operator x [N, C, H, W] -> `op.blur.blur2d(x[:, channels], taps, stride)`
+    (all channels with channels=None): `channels=[0]` is a blurred, low-resolution density
+    image.  Pass it as `LETKF(..., observe=..., obs_stride=stride)`; blur2d samples at
+    stride * i + (stride - 1) // 2, the default `obs_offset`.  The footprint of an observation
+    is len(taps) // 2 grid points around its sampling point, where the filter localizes it:
+    keep it small against the radius R."""
+    from op import blur
+    idx = None if channels is None else [int(c) for c in channels]
+
+    def observe(x):
+        return blur.blur2d(x if idx is None else x[:, idx].contiguous(), taps, stride)
+    return observe
+
+
 class LETKF:
     """members: ensemble size m (2..64).  radius: window half-width R in grid points (0..8).
     taper: "gaspari_cohn" (with `cutoff`, default (R + 1) / 2), "boxcar", or a [2R+1, 2R+1]
@@ -52,11 +74,20 @@ class LETKF:
     step_fn(f, v, p) -> (f', v', p') on [B * m] planes; default `ns_step.full_step(compat=False)`
     with this object's dt, dx (HIP tensors only).  analysis_fn(ens, obs, prec, taper, inflation)
     -> (ens_out, status); default `op.letkf.analysis` (HIP, float32).  Restatements of both can
-    be passed to run the host logic on other devices or dtypes."""
+    be passed to run the host logic on other devices or dtypes.
+
+    observe: None (the masked identity: nothing below applies), or a map of planes
+    [N, C, H, W] -> [N, Cy, Hy, Wy] such as `blur_observation`.  Observation (i, j) is localized
+    at state grid point (obs_stride i + obs_offset, obs_stride j + obs_offset); obs_offset=None:
+    (obs_stride - 1) // 2.  Its footprint should be small against R; with a window that sees
+    everything the analysis is the exact Kalman update for any linear `observe`.
+    obs_analysis_fn(ens, yens, obs, prec, taper, inflation, stride, offset) -> (ens_out, status);
+    default `op.letkf.analysis_obs`."""
 
     def __init__(self, members, radius, cutoff=None, inflation=1.0, taper="gaspari_cohn",
                  steps_per_frame=1, dt=simulator.dt, dx=simulator.dx, step_fn=None,
-                 analysis_fn=None):
+                 analysis_fn=None, observe=None, obs_stride=1, obs_offset=None,
+                 obs_analysis_fn=None):
         from op import letkf as K
         if not 2 <= int(members) <= K.MAX_MEMBERS:
             raise ValueError(f"LETKF: members = {members} out of range [2, {K.MAX_MEMBERS}]")
@@ -82,6 +113,15 @@ class LETKF:
         self.radius = self.taper.shape[0] // 2
         self.step_fn = simulator.default_step(self.dt, self.dx) if step_fn is None else step_fn
         self.analysis_fn = K.analysis if analysis_fn is None else analysis_fn
+        self.observe = observe
+        self.obs_stride = int(obs_stride)
+        if self.obs_stride != obs_stride or self.obs_stride < 1:
+            raise ValueError(f"LETKF: obs_stride = {obs_stride} must be an integer >= 1")
+        self.obs_offset = (self.obs_stride - 1) // 2 if obs_offset is None else int(obs_offset)
+        if not 0 <= self.obs_offset < self.obs_stride:
+            raise ValueError(f"LETKF: obs_offset = {obs_offset} out of range "
+                             f"[0, obs_stride = {self.obs_stride})")
+        self.obs_analysis_fn = K.analysis_obs if obs_analysis_fn is None else obs_analysis_fn
         self.ens = None
 
     # ------------------------------------------------------------------------------------
@@ -131,6 +171,16 @@ class LETKF:
         return self._need().std(1, unbiased=True)
 
     @torch.no_grad()
+    def observation_shape(self):
+        """(B, Cy, Hy, Wy): what `observe` makes of one member of every sample ((B, C, H, W)
+        without `observe`)."""
+        ens = self._need()
+        B, m, C, H, W = ens.shape
+        if self.observe is None:
+            return (B, C, H, W)
+        return (B,) + tuple(self.observe(ens[:, 0].contiguous()).shape[1:])
+
+    @torch.no_grad()
     def forecast(self):
         """`steps_per_frame` simulator steps of every member."""
         ens = self._need()
@@ -142,22 +192,33 @@ class LETKF:
 
     @torch.no_grad()
     def analyze(self, obs, weights, valid=None):
-        """obs [B, 4, H, W]; weights: inverse variances broadcastable to it (0 = unobserved;
-        obs may hold anything there).  valid: None, or a bool [B] device mask -- a sample that
-        is not valid keeps its forecast bit for bit (no analysis, no inflation).
+        """obs [B, 4, H, W] ([B, Cy, Hy, Wy] with `observe`); weights: inverse variances
+        broadcastable to it (0 = unobserved; obs may hold anything there).  valid: None, or a
+        bool [B] device mask -- a sample that is not valid keeps its forecast bit for bit (no
+        analysis, no inflation).
         -> status int32 [B, H, W] (0 for samples that are not valid)."""
         ens = self._need()
         B, m, C, H, W = ens.shape
-        if tuple(obs.shape) != (B, C, H, W):
-            raise ValueError(f"LETKF: obs must be {[B, C, H, W]}, got {list(obs.shape)}")
+        yens = None
+        if self.observe is not None:
+            yens = self.observe(ens.reshape(B * m, C, H, W))
+            yens = yens.reshape(B, m, *yens.shape[1:]).contiguous()
+        oshape = (B, C, H, W) if yens is None else (B,) + tuple(yens.shape[2:])
+        if tuple(obs.shape) != oshape:
+            raise ValueError(f"LETKF: obs must be {list(oshape)}, got {list(obs.shape)}")
         prec = torch.as_tensor(weights, dtype=ens.dtype, device=ens.device)
         if prec.ndim == 5 and prec.shape[0] == 1:  # observation_weights' frame axis
             prec = prec[0]
-        prec = prec.expand(B, C, H, W)
+        prec = prec.expand(oshape)
         if valid is not None:
             prec = prec * valid.view(B, 1, 1, 1).to(ens.dtype)
-        out, status = self.analysis_fn(ens.contiguous(), obs.contiguous(), prec.contiguous(),
-                                       self.taper, self.inflation)
+        if yens is None:
+            out, status = self.analysis_fn(ens.contiguous(), obs.contiguous(), prec.contiguous(),
+                                           self.taper, self.inflation)
+        else:
+            out, status = self.obs_analysis_fn(ens.contiguous(), yens, obs.contiguous(),
+                                               prec.contiguous(), self.taper, self.inflation,
+                                               self.obs_stride, self.obs_offset)
         if valid is not None:
             out = torch.where(valid.view(B, 1, 1, 1, 1), out, ens)
             status = status * valid.view(B, 1, 1).to(status.dtype)
@@ -166,12 +227,19 @@ class LETKF:
 
     @torch.no_grad()
     def filter(self, obsv_seq, weights, valid=None, keep_ensembles=False):
-        """Forecast + analysis for every frame of obsv_seq [T, B, 4, H, W] from the current
-        ensemble.  weights: as `analyze` (broadcast over the frames).  valid: None, bool [T] or
-        bool [T, B] as `UKF.filter` takes it; a missing frame is forecast only.
+        """Forecast + analysis for every frame of obsv_seq [T, B, 4, H, W] ([T, B, Cy, Hy, Wy]
+        with `observe`) from the current ensemble.  weights: as `analyze` (broadcast over the
+        frames).  valid: None, bool [T] or bool [T, B] as `UKF.filter` takes it; a missing frame
+        is forecast only.
         -> EnsembleHistory."""
         ens = self._need()
-        if obsv_seq.ndim != 5 or tuple(obsv_seq.shape[1:]) != (ens.shape[0],) + tuple(ens.shape[2:]):
+        if self.observe is not None:
+            want = self.observation_shape()
+            if obsv_seq.ndim != 5 or tuple(obsv_seq.shape[1:]) != want:
+                raise ValueError(f"LETKF.filter: obsv_seq must be [T, B, Cy, Hy, Wy] with "
+                                 f"[B, Cy, Hy, Wy] = {list(want)}, the observed ensemble's, got "
+                                 f"{list(obsv_seq.shape)}")
+        elif obsv_seq.ndim != 5 or tuple(obsv_seq.shape[1:]) != (ens.shape[0],) + tuple(ens.shape[2:]):
             raise ValueError(f"LETKF.filter: obsv_seq must be [T, B, C, H, W] of the ensemble, got "
                              f"{list(obsv_seq.shape)}")
         T, B = obsv_seq.shape[:2]

@@ -1000,6 +1000,41 @@ int bpk_letkf_analysis_f32(const float* ens, const float* obs, const float* prec
                            int64_t B, int m, int C, int H, int W, int R, float inflation,
                            void* stream);
 
+/* The same analysis for observations on a grid of their own, behind any operator h: the caller
+ * passes the members in observation space, and the state is updated at every grid point.  The
+ * truth is the float64 restatement tests/letkf_obs_ref.py.
+ *   ens   [B, m, C, H, W]     background state ensemble, 2 <= m <= 64, 1 <= C <= 8
+ *   yens  [B, m, Cy, Hy, Wy]  the same members in observation space, yens_k = h(ens_k),
+ *                             1 <= Cy <= 8; may alias ens
+ *   obs, prec [B, Cy, Hy, Wy] observations and their inverse variances, 0 = unobserved
+ *   taper [2R+1, 2R+1]        localization weights in state-grid units, as above
+ *   ens_out [B, m, C, H, W], status int32 [B, H, W]
+ * Observation (i, j) sits at state grid point (stride i + offset, stride j + offset) -- the
+ * sampling of bpk_blur2d with offset = (stride - 1) / 2 -- with stride >= 1,
+ * 0 <= offset < stride, and stride (Hy - 1) + offset <= H - 1, stride (Wy - 1) + offset <= W - 1.
+ * For every (b, y0, x0), with ybar the member mean of yens, dY_k = yens_k - ybar, and
+ * rho_j = taper[y - y0 + R, x - x0 + R] * prec_j for the observation j = (c, i, j) whose
+ * position (y, x) lies in the window |y - y0| <= R, |x - x0| <= R:
+ *   A  = (m-1)/inflation I + sum_j rho_j dY_j dY_j^T,   g = sum_j rho_j dY_j (obs_j - ybar_j)
+ * then A = Q L Q^T, wbar, Wa and the update of the C state channels at (y0, x0) from the state
+ * perturbations dX exactly as above; entries with rho_j == 0 are skipped, and status and the
+ * fall-back are as above.  The window is walked in the same order with the same roundings:
+ * with yens == ens, Cy == C, stride 1, offset 0 the result equals bpk_letkf_analysis_f32's
+ * bit for bit.
+ * ens_out must alias neither ens nor yens.  B H W and B Hy Wy are below 2^31.
+ * `workspace`: bpk_letkf_obs_workspace_bytes(...) bytes, both means and both member-innermost
+ * perturbation arrays: (1 + MP) (B C H W + B Cy Hy Wy) floats, MP = m padded to 8 / 16 / 32 /
+ * 64; the query returns -1 for sizes out of range.
+ * Arguments are validated before any device call.  Three launches, no atomics, every
+ * reduction in a fixed order (bit-reproducible), asynchronous on `stream`. */
+int64_t bpk_letkf_obs_workspace_bytes(int64_t B, int m, int C, int H, int W, int Cy, int Hy,
+                                      int Wy);
+int bpk_letkf_analysis_obs_f32(const float* ens, const float* yens, const float* obs,
+                               const float* prec, const float* taper, float* ens_out, int* status,
+                               void* workspace, int64_t B, int m, int C, int H, int W, int Cy,
+                               int Hy, int Wy, int stride, int offset, int R, float inflation,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

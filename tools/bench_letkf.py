@@ -12,6 +12,14 @@ the same way with --basis-reps visits; it is skipped, and the output says so, wh
 (memory, an unsupported batch) or where one call took longer than --basis-budget seconds at a
 smaller shape.  The basis is never an earlier state of the kernel.
 
+With --obs-stride S [S ...] the same shapes are also timed through `op.letkf.analysis_obs`: the
+density (channel 0) observed through a 5-tap Gaussian blur (`op.blur.blur2d`, variance 1) and
+decimated at each stride S, under a random half mask on the observation grid, sigma = 0.02.  The
+members' images yens are formed once outside the timed call (the time of that blur is reported
+as observe_ms).  --obs-identity adds `analysis_obs` with yens = ens, stride 1 on the "density"
+pattern: the work of `analysis` plus one launch.  These lines say "letkf.analysis_obs" and
+carry no basis.
+
 The kernel does not report its sweep count; with --ref-sweeps the float32 restatement
 tests/letkf_ref.py (same rotation order and threshold, on the CPU) counts sweeps on a
 12 x 12 crop of the same inputs.
@@ -19,7 +27,8 @@ tests/letkf_ref.py (same rotation order and threshold, on the CPU) counts sweeps
 Prints one JSON line per configuration and a last line with the device name.
 
     python tools/bench_letkf.py [--size 192] [--reps 20] [--warmup 3] [--basis-reps 3]
-                                [--no-basis] [--ref-sweeps] [--out FILE]
+                                [--no-basis] [--ref-sweeps] [--obs-stride S [S ...]]
+                                [--obs-identity] [--out FILE]
 """
 import argparse
 import json
@@ -66,6 +75,22 @@ def make_inputs(size, m, pattern, dev):
     else:
         prec[:] = 1 / sigma ** 2
     return ens.to(dev), obs.to(dev), prec.to(dev)
+
+
+def make_obs_inputs(size, m, stride, dev):
+    """The ensemble of make_inputs(..., "density"), its density observed through a 5-tap
+    Gaussian blur at `stride`: (ens, yens [1, m, 1, Hy, Wy], obs, prec [1, 1, Hy, Wy])."""
+    from op import blur
+    ens = make_inputs(size, m, "density", dev)[0]
+    taps = blur.gaussian_taps(1.0, 5)
+    g = torch.Generator().manual_seed(7000 * m + size + stride)
+    yens = blur.blur2d(ens[0, :, 0:1].contiguous(), taps, stride).unsqueeze(0).contiguous()
+    sigma = 0.02
+    shape = (1,) + tuple(yens.shape[2:])
+    obs = yens.mean(1) + (sigma * torch.randn(shape, generator=g)).to(dev)
+    prec = ((torch.rand(shape, generator=g) < 0.5).float() / sigma ** 2).to(dev)
+    obs[prec == 0] = float("nan")
+    return ens, yens, obs, prec, taps
 
 
 def composition(ens, obs, prec, taper, inflation):
@@ -115,6 +140,8 @@ def main():
     ap.add_argument("--no-basis", action="store_true")
     ap.add_argument("--ref-sweeps", action="store_true")
     ap.add_argument("--inflation", type=float, default=1.05)
+    ap.add_argument("--obs-stride", type=int, nargs="*", default=[])
+    ap.add_argument("--obs-identity", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")  # no fall-back: a timing needs the device
@@ -126,9 +153,27 @@ def main():
                 cfgs.append(dict(m=m, R=R, pattern=pattern, data=data,
                                  taper=K.gaspari_cohn_taper(R).to(dev), t=[], tf=[], tb=[],
                                  basis=None))
+    no_basis = "not run (the basis restates the identity observation only)"
+    for m in a.members:
+        obs_data = [(s, "blur5") + make_obs_inputs(a.size, m, s, dev) for s in a.obs_stride]
+        if a.obs_identity:
+            ens, obs, prec = make_inputs(a.size, m, "density", dev)
+            obs_data.append((1, "ens", ens, ens, obs, prec, None))
+        for s, yname, ens, yens, obs, prec, taps in obs_data:
+            for R in a.radii:
+                cfgs.append(dict(m=m, R=R, pattern="density", data=(ens, yens, obs, prec),
+                                 obs_stride=s, yens=yname, taps=taps,
+                                 taper=K.gaspari_cohn_taper(R).to(dev), t=[], tf=[], tb=[], to=[],
+                                 basis=no_basis))
 
     def analysis(c):
+        if "obs_stride" in c:
+            return K.analysis_obs(*c["data"], c["taper"], a.inflation, c["obs_stride"])
         return K.analysis(*c["data"], c["taper"], a.inflation)
+
+    def observe(c):
+        from op import blur
+        return blur.blur2d(c["data"][0][0, :, 0:1].contiguous(), c["taps"], c["obs_stride"])
 
     def forecast(c):
         p = c["data"][0][0]
@@ -147,6 +192,8 @@ def main():
         for c in cfgs:
             c["t"].append(timed(lambda: analysis(c))[0])
             c["tf"].append(timed(lambda: forecast(c))[0])
+            if c.get("taps") is not None:
+                c["to"].append(timed(lambda: observe(c))[0])
 
     if not a.no_basis:
         # a small shape first: if one call there is already over budget, the full one is not tried
@@ -197,7 +244,12 @@ def main():
                "us_per_grid_point": round(1e3 * statistics.median(c["t"]) / sites, 4),
                "forecast_step_ms": med(c["tf"]), "flagged": c["flagged"], "finite": c["finite"],
                "reps": a.reps}
-        if a.no_basis:
+        if "obs_stride" in c:
+            res.update({"what": "letkf.analysis_obs", "obs_stride": c["obs_stride"],
+                        "yens": c["yens"], "obs_grid": list(c["data"][1].shape[3:])})
+            if c["to"]:
+                res["observe_ms"] = med(c["to"])
+        if a.no_basis and "obs_stride" not in c:
             res["basis"] = "not run (--no-basis)"
         elif c["tb"]:
             res["basis"] = {"what": "torch: unfold + einsum + batched linalg.eigh, same device",
@@ -206,7 +258,7 @@ def main():
             res["speedup_vs_basis"] = round(statistics.median(c["tb"]) / statistics.median(c["t"]), 1)
         else:
             res["basis"] = c["basis"]
-        if a.ref_sweeps:
+        if a.ref_sweeps and "obs_stride" not in c:
             import letkf_ref
             ens, obs, prec = (v[..., :12, :12].cpu().numpy() for v in c["data"])
             _, st, sw = letkf_ref.ref32(ens, obs, prec, c["taper"].cpu().numpy(), a.inflation, True)
