@@ -8,8 +8,8 @@ continuous, likelihood_weighting)` -> `step_fn(state, batch)` with
 state = {'optimizer', 'model', 'ema', 'step'}.
 
 MI355X notes: the model runs on the fused HIP block ops; Adam uses the
-fused multi-tensor implementation on the GPU (BPK_ADAM_FUSED=0: foreach); for batch-sharded data parallelism wrap
-the model in torch DistributedDataParallel (RCCL all-reduce of the gradient
+fused multi-tensor implementation on the GPU (foreach for CPU parameters); for
+batch-sharded data parallelism wrap the model in torch DistributedDataParallel (RCCL all-reduce of the gradient
 buckets, overlapped with backward) -- each rank's loss is the mean over its
 shard, so the averaged gradient equals the single-process full-batch gradient.
 The PINN step functions live in pinn_kalman/.
@@ -26,9 +26,6 @@ from models import utils as mutils
 from sde_lib import VESDE, VPSDE
 
 
-_ADAM_FUSED = True
-
-
 def get_optimizer(config, params, lr_mul=1.0, is_bpinn=False):
     lr = config.optim.bpinn_lr if is_bpinn else config.optim.lr
     decay = config.optim.bpinn_weight_decay if is_bpinn else config.optim.weight_decay
@@ -38,7 +35,7 @@ def get_optimizer(config, params, lr_mul=1.0, is_bpinn=False):
     # on the GPU: the fused (single multi-tensor kernel per step) Adam, which also keeps the
     # per-parameter step counts and bias corrections on the device -- the foreach form
     # spends ~ms of host time per step on them for the ~700 NCSN++ tensors
-    fused = _ADAM_FUSED and len(params) > 0 and all(
+    fused = len(params) > 0 and all(
         (p["params"][0] if isinstance(p, dict) else p).is_cuda for p in params)
     kind = dict(fused=True) if fused else dict(foreach=True)
     return optim.Adam(params, lr=lr * lr_mul, betas=(config.optim.beta1, 0.999),

@@ -17,7 +17,6 @@ Call sites of the native ops: `project` -> op.grid_sample.grid_sample_2d
 from __future__ import annotations
 
 import functools
-import os
 
 import torch
 import torch.nn as nn
@@ -29,8 +28,6 @@ from op.fused_act import LeakyReLU, leaky_relu
 from . import layers
 
 _BASE_GRIDS: dict = {}
-# FlowNet: the two frames' feature pyramids as one batch (A/B switch; tests flip it)
-_PAIR_FRAMES = os.environ.get("BPK_PAIR_FRAMES", "1") == "1"
 
 
 def _base_grid(shape, device):
@@ -227,7 +224,7 @@ class FlowNet(nn.Module):
 
     def forward(self, f1, f2, x, y, t, size=None):
         emb = self.feature_extractor.embeddings(x, y, t, f1.shape[1])
-        if _PAIR_FRAMES and f1.is_cuda:
+        if f1.is_cuda:
             # both frames through the shared extractor as one batch (forward_frames)
             p1, p2 = self.feature_extractor.forward_frames(torch.stack([f1, f2]), emb)
         else:

@@ -21,6 +21,24 @@ from op import matmul as matmul_op
 from op import norm_act as norm_act_op
 from op.norm_act import ACT_NONE, ACT_SILU, group_norm_act, group_norm_affine, residual_rescale
 
+# Test seams: plain constants, all on.  A test sets one to False to run the unfused composition
+# beside the fused path (each fusion measured against it: DESIGN.md section 4).
+_WINO_ENABLED = True  # convs on the native kernels, False: MIOpen (test_gpu_configs)
+_IN_FUSED = True      # InstanceNorm+ELU and its backwards, one kernel each (test_gpu_ops)
+_IN_FANOUT = True     # ResidualBlock input: gradients added in the norm's backward (test_gpu_ops)
+_DDPM_FUSED = True    # ResnetBlockDDPM inference on the GroupNorm-prologue convs (test_gpu_models)
+_TEMB_FOLD = True     # inference TembBank kept, Conv_0.bias folded in (test_gpu_resample_block)
+_SKIP_LINK = True     # eval autograd: Conv_1's skip gradient joins Conv_0's backward (test_gpu_ops)
+_SEMB_FUSED = True    # spatial embedding as one native op (test_gpu_spatial_emb, test_gpu_pinn)
+# Public switches, read from the environment at import; test_gpu_ops and
+# tools/diag_gn_fanout.py flip them too.
+# eval-mode autograd (DPS): GroupNorm+SiLU inside the conv's input load.  Its backward is
+# first-order only (once_differentiable): create_graph=True / higher derivatives through an
+# eval-mode score net need BPK_GN_CONV_AD=0 or the `higher_order_autograd()` block below
+_GN_CONV_AD = os.environ.get("BPK_GN_CONV_AD", "1") == "1"
+# a block input's skip gradient added inside the GroupNorm backward kernel (gn_act_fanout)
+_GN_FANOUT = os.environ.get("BPK_GN_FANOUT", "1") == "1"
+
 
 def get_act(config):
     """Activation module from config.model.nonlinearity (reference layers.py:29-41)."""
@@ -39,10 +57,6 @@ def dense(m: nn.Linear, x):
     if x.is_cuda and matmul_op.supported(x, m.weight, m.bias):
         return matmul_op.linear(x, m.weight, m.bias)
     return m(x)
-
-
-# the bank under autograd too (training, DPS); A/B switch
-_TEMB_BANK_AD = os.environ.get("BPK_TEMB_BANK_AD", "1") == "1"
 
 
 class TembBank:
@@ -115,11 +129,6 @@ def temb_proj(dense_m: nn.Linear, act, temb):
     return dense(dense_m, act(temb))
 
 
-# inference: the concatenated Dense_0 weights / biases of the TembBank kept between forwards,
-# Conv_0.bias folded into the bias; read once at import (with BPK_WEIGHT_CACHE, op.conv)
-_TEMB_FOLD = os.environ.get("BPK_TEMB_FOLD", "1") == "1"
-
-
 def conv_temb_bias(block: nn.Module, act, temb, n):
     """The per-(n, c) bias that follows a residual block's Conv_0: Conv_0.bias[None, :] +
     Dense_0(act(temb)) [n, C] (Conv_0.bias alone, broadcast, without temb) -- one TembBank
@@ -130,9 +139,6 @@ def conv_temb_bias(block: nn.Module, act, temb, n):
     if temb is not None:
         bias_nc = bias_nc + temb_proj(block.Dense_0, act, temb)
     return bias_nc
-
-
-_GN_FANOUT = os.environ.get("BPK_GN_FANOUT", "1") == "1"  # A/B switch (gn_act_fanout)
 
 
 def gn_act_fanout(x, gn: nn.GroupNorm, act=None):
@@ -189,21 +195,6 @@ def ddpm_conv1x1(in_planes, out_planes, stride=1, bias=True, init_scale=1., padd
     return conv
 
 
-# Fusion switches: module constants (each measured against the unfused form, DESIGN.md
-# section 4); tests flip them to compare against the unfused composition.
-_WINO_ENABLED = True  # 3x3 convs on the Winograd kernels (False: MIOpen)
-_IN_FUSED = True      # InstanceNorm+ELU (+ backward, double backward) as one kernel each
-_GN_STATS = True      # GroupNorm partial statistics from the producing conv's epilogue
-_GEMM1X1 = True       # 1x1 convs on the MFMA GEMM kernels
-_DDPM_FUSED = True    # ResnetBlockDDPM inference on the GroupNorm-prologue Winograd convs
-# eval-mode autograd (DPS): GroupNorm+SiLU inside the conv's input load.  Its backward is
-# first-order only (once_differentiable): create_graph=True / higher derivatives through an
-# eval-mode score net need BPK_GN_CONV_AD=0 or the `higher_order_autograd()` block below
-_GN_CONV_AD = os.environ.get("BPK_GN_CONV_AD", "1") == "1"
-# the same under training (A/B switch, BPK_GN_CONV_AD_TRAIN=1)
-_GN_CONV_AD_TRAIN = os.environ.get("BPK_GN_CONV_AD_TRAIN", "0") == "1"
-
-
 def _is_3x3(x, conv: nn.Conv2d):
     return (_WINO_ENABLED and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
@@ -211,7 +202,7 @@ def _is_3x3(x, conv: nn.Conv2d):
 
 
 def _is_1x1(x, conv: nn.Conv2d):
-    return (_WINO_ENABLED and _GEMM1X1 and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+    return (_WINO_ENABLED and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
             and conv.padding == (0, 0) and conv.groups == 1 and x.is_cuda)
 
 
@@ -258,7 +249,7 @@ def gn_silu_conv(x, gn: nn.GroupNorm, conv: nn.Conv2d, bias_nc=None, conv_bias=N
         return None  # the small-Cin kernel has no GroupNorm prologue
     ss = group_norm_affine(x, gn, bias_nc)
     return conv_op.conv3x3(x, conv.weight, conv_bias, skip=skip, div=div, pre=ss,
-                           stats=_GN_STATS and conv_op.wino_supported(x, conv.weight))
+                           stats=conv_op.wino_supported(x, conv.weight))
 
 
 def gn_silu_conv_ad(module: nn.Module, x, gn: nn.GroupNorm, conv: nn.Conv2d, act, bias_nc=None,
@@ -274,7 +265,7 @@ def gn_silu_conv_ad(module: nn.Module, x, gn: nn.GroupNorm, conv: nn.Conv2d, act
     Returns (output, x') or None; x' is x itself, or with fanout=True (a block whose shortcut
     conv reads x) x through the fused Function, so the shortcut's gradient joins the GroupNorm
     backward's pass instead of an accumulation launch."""
-    if not (_GN_CONV_AD and (not module.training or _GN_CONV_AD_TRAIN) and torch.is_grad_enabled()
+    if not (_GN_CONV_AD and not module.training and torch.is_grad_enabled()
             and isinstance(act, nn.SiLU) and _is_3x3(x, conv)):
         return None
     if skip is not None and skip.shape[1] != conv.out_channels:
@@ -317,11 +308,6 @@ def skip_link(module: nn.Module, identity_skip: bool):
                                   and torch.is_grad_enabled()) else None
 
 
-_SKIP_LINK = os.environ.get("BPK_SKIP_LINK", "1") == "1"  # A/B switch
-# ResidualBlock (PressureNet): the input's two gradients added in the norm's backward kernel
-_IN_FANOUT = os.environ.get("BPK_IN_FANOUT", "1") == "1"
-
-
 def _dropout_off(m: nn.Dropout) -> bool:
     return not m.training or m.p == 0
 
@@ -332,7 +318,7 @@ def conv_residual(h, conv: nn.Conv2d, bias, skip, div, stats=False):
     stats=True (inference): the output carries GroupNorm partial statistics."""
     if _wino_eligible(h, conv) and skip.shape[1] == conv.out_channels:
         return conv_op.conv3x3(h, conv.weight, bias, skip=skip, div=div,
-                               stats=_GN_STATS and stats and conv_op.wino_supported(h, conv.weight))
+                               stats=stats and conv_op.wino_supported(h, conv.weight))
     return residual_rescale(skip, conv2d(h, conv, bias=False), bias, div)
 
 
@@ -344,6 +330,68 @@ def cat_channels(a, b):
     if pa is not None and pb is not None and pa[1:] == pb[1:]:
         conv_op.attach_gn_partials(y, torch.cat([pa[0], pb[0]], dim=1), pa[1], pa[2])
     return y
+
+
+# ---- pieces shared by ResnetBlockDDPM and layerspp.ResnetBlockBigGANpp (GroupNorm_0, Conv_0,
+# Dense_0, GroupNorm_1, Dropout_0, Conv_1, act, in_ch, out_ch)
+
+def pair_conv0(block, x1, x2, eligible, skip_conv=None):
+    """Conv_0(SiLU(GroupNorm_0([x1, x2]))) without bias at inference, the concatenation never
+    built: GroupNorm_0's table from both parts' partial statistics (one read of a part whose
+    producer wrote none: still cheaper than concatenating and reading the concatenation),
+    Conv_0 reading both sources, its output carrying GroupNorm_1's partials.  None when a
+    piece does not fit (`eligible`: the block's own condition; skip_conv: a 1x1 skip
+    projection that must take the two sources too) -- the caller then concatenates."""
+    N, C1, H, W = x1.shape
+    C = C1 + x2.shape[1]
+    if not (eligible and C == block.in_ch and C1 % 8 == 0 and x1.is_cuda
+            and x1.dtype == torch.float32
+            and bool(conv_op.lib.bpk_conv3x3_wino_supported(N, C, block.out_ch, H, W))
+            and (skip_conv is None or conv_op.gemm1x1_supported(x1, skip_conv.weight, x2))):
+        return None
+    p1, p2 = conv_op.ensure_gn_partials(x1), conv_op.ensure_gn_partials(x2)
+    if p1 is None or p2 is None or p1[1:] != p2[1:]:
+        return None
+    ss = norm_act_op.group_norm_affine_partials(p1, N, C, block.GroupNorm_0, part2=p2)
+    return conv_op.conv3x3_pair(x1, x2, block.Conv_0.weight, pre=ss, stats=True)
+
+
+def inference_tail(block, h, bias_nc, bias, skip, div, stats):
+    """(skip + Conv_1(SiLU(GroupNorm_1(h + bias_nc))) + bias) / div at inference: the
+    statistics pass and the Winograd conv (gn_silu_conv), else gn_act + conv_residual
+    (stats: its output carries GroupNorm partials)."""
+    out = gn_silu_conv(h, block.GroupNorm_1, block.Conv_1, bias_nc, bias, skip, div)
+    if out is not None:
+        return out
+    h = gn_act(h, block.GroupNorm_1, block.act, bias_nc)
+    return conv_residual(h, block.Conv_1, bias, skip, div, stats=stats)
+
+
+def autograd_conv0(block, x):
+    """(Conv_0(act(GroupNorm_0(x))) without bias, x for the shortcut, SkipLink or None) under
+    autograd: the fused first-order Function for an eval-mode block (gn_silu_conv_ad), the
+    link made when the skip is x itself and Conv_1 can take the fused form too; else the
+    unfused composition."""
+    identity = block.in_ch == block.out_ch
+    link = skip_link(block, identity and _dropout_off(block.Dropout_0))
+    r = gn_silu_conv_ad(block, x, block.GroupNorm_0, block.Conv_0, block.act, take=link,
+                        fanout=not identity)
+    if r is not None:
+        return r + (link,)
+    h, x = gn_act_fanout(x, block.GroupNorm_0, block.act)
+    return conv_nobias(h, block.Conv_0), x, None
+
+
+def autograd_tail(block, h, bias_nc, bias, skip, div, link):
+    """inference_tail under autograd: the fused Function when dropout is off (handing its skip
+    gradient to `link`), else GroupNorm_1 + act, dropout, Conv_1 + residual."""
+    if _dropout_off(block.Dropout_0):
+        out = gn_silu_conv_ad_1(block, h, block.GroupNorm_1, block.Conv_1, block.act,
+                                bias_nc=bias_nc, conv_bias=bias, skip=skip, div=div, give=link)
+        if out is not None:
+            return out
+    h = gn_act(h, block.GroupNorm_1, block.act, bias_nc)
+    return conv_residual(block.Dropout_0(h), block.Conv_1, bias, skip, div)
 
 
 class Conv2d(nn.Conv2d):
@@ -437,10 +485,6 @@ def _max_minus(v):
     return (m - g).reshape(v.shape)
 
 
-_SEMB_FUSED = os.environ.get("BPK_SEMB_FUSED", "1") == "1"  # A/B switch
-_RES_TAIL = os.environ.get("BPK_RES_TAIL", "1") == "1"  # ResidualBlock: skip add in conv2
-
-
 def get_timestep_embeddings(timesteps, dims, max_positions=10000):
     """[get_timestep_embedding(timesteps, d) for d in dims] (the same values) with one product,
     one sin and one cos for all of them: FlowNet embeds t at every pyramid level, and the PINN
@@ -494,7 +538,7 @@ class NIN(nn.Module):
         # 1x1 convolution with weight W^T: the MFMA GEMM kernels (forward and every
         # derivative, op.conv.conv1x1_ad) on HIP tensors
         w = self.W.t()
-        if _GEMM1X1 and x.is_cuda and conv_op.conv1x1_train_supported(x, w):
+        if x.is_cuda and conv_op.conv1x1_train_supported(x, w):
             return conv_op.conv1x1_ad(x, w, self.b)
         if _WINO_ENABLED and x.is_cuda:
             # planes the 1x1 GEMM does not take (H * W % 128: the 4 x 4 attention of the
@@ -532,8 +576,8 @@ class AttnBlock(nn.Module):
         h = gn_act(x, self.GroupNorm_0, None)
         if _DDPM_FUSED and not torch.is_grad_enabled():
             # inference: AttnBlockpp's stacked q/k/v MFMA GEMM (the same NIN_0..3 layout)
-            from .layerspp import _ATTN_QKV, AttnBlockpp
-            if _ATTN_QKV and AttnBlockpp._qkv_ok(self, h):
+            from .layerspp import AttnBlockpp
+            if AttnBlockpp._qkv_ok(self, h):
                 return residual_rescale(x, AttnBlockpp._forward_qkv(self, h), None, 1.0)
         h = self.NIN_3(_attention(h, self.NIN_0, self.NIN_1, self.NIN_2))
         return residual_rescale(x, h, None, 1.0)
@@ -605,77 +649,49 @@ class ResnetBlockDDPM(nn.Module):
     def forward(self, x, temb=None):
         assert x.shape[1] == self.in_ch
         if _DDPM_FUSED and fused_inference_ok(self, x, self.act):
-            # inference (the nc_ddpmpp sampler): GroupNorm_0+SiLU inside Conv_0's input load
-            h = gn_silu_conv(x, self.GroupNorm_0, self.Conv_0)
-            if h is None:
-                h = conv_nobias(gn_act(x, self.GroupNorm_0, self.act), self.Conv_0)
-            return self._fused_tail(h, x, None, temb)
-        link = skip_link(self, self.in_ch == self.out_ch and _dropout_off(self.Dropout_0))
-        r = gn_silu_conv_ad(self, x, self.GroupNorm_0, self.Conv_0, self.act, take=link,
-                            fanout=self.in_ch != self.out_ch)
-        if r is None:
-            link = None
-            h, x = gn_act_fanout(x, self.GroupNorm_0, self.act)
-            h = conv_nobias(h, self.Conv_0)
-        else:
-            h, x = r
-        bias_nc = self.Conv_0.bias[None, :].expand(x.shape[0], -1)
-        if temb is not None:
-            bias_nc = bias_nc + temb_proj(self.Dense_0, self.act, temb)
+            return self._inference(x, temb)
+        return self._autograd(x, temb)
+
+    def _inference(self, x, temb):
+        """the nc_ddpmpp sampler: GroupNorm_0+SiLU inside Conv_0's input load"""
+        h = gn_silu_conv(x, self.GroupNorm_0, self.Conv_0)
+        if h is None:
+            h = conv_nobias(gn_act(x, self.GroupNorm_0, self.act), self.Conv_0)
+        return self._shortcut_and_tail(h, x, None, temb)
+
+    def _autograd(self, x, temb):
+        """training, and eval-mode gradients (DPS) on the fused first-order Function"""
+        h, x, link = autograd_conv0(self, x)
+        bias_nc = conv_temb_bias(self, self.act, temb, x.shape[0])
         if self.in_ch != self.out_ch:
             x = self.Conv_2(x) if self.conv_shortcut else self.NIN_0(x)
-        if _dropout_off(self.Dropout_0):
-            out = gn_silu_conv_ad_1(self, h, self.GroupNorm_1, self.Conv_1, self.act,
-                                    bias_nc=bias_nc, conv_bias=self.Conv_1.bias, skip=x, div=1.0,
-                                    give=link)
-            if out is not None:
-                return out
-        h = gn_act(h, self.GroupNorm_1, self.act, bias_nc)
-        h = self.Dropout_0(h)
-        return conv_residual(h, self.Conv_1, self.Conv_1.bias, x, 1.0)
+        return autograd_tail(self, h, bias_nc, self.Conv_1.bias, x, 1.0, link)
 
     def forward_pair(self, x1, x2, temb=None):
         """forward(torch.cat([x1, x2], 1), temb) -- the up path's skip concatenation -- at
-        inference without building it: GroupNorm_0 from both parts' partial statistics,
-        Conv_0 reading both sources, NIN_0 as one two-source MFMA GEMM (as
+        inference without building it (pair_conv0), NIN_0 as one two-source MFMA GEMM (as
         ResnetBlockBigGANpp.forward_pair); the concatenation when a piece does not fit."""
-        N, C1, H, W = x1.shape
-        C = C1 + x2.shape[1]
-        ok = (_DDPM_FUSED and fused_inference_ok(self, x1, self.act)
-              and fused_inference_ok(self, x2, self.act) and C == self.in_ch and C1 % 8 == 0
-              and x1.is_cuda and x1.dtype == torch.float32
-              and bool(conv_op.lib.bpk_conv3x3_wino_supported(N, C, self.out_ch, H, W)))
-        if ok:
-            p1, p2 = conv_op.ensure_gn_partials(x1), conv_op.ensure_gn_partials(x2)
-            ok = p1 is not None and p2 is not None and p1[1:] == p2[1:]
-        if not ok:
+        h = pair_conv0(self, x1, x2, _DDPM_FUSED and fused_inference_ok(self, x1, self.act)
+                       and fused_inference_ok(self, x2, self.act))
+        if h is None:
             return self.forward(cat_channels(x1, x2), temb)
-        ss = norm_act_op.group_norm_affine_partials(p1, N, C, self.GroupNorm_0, part2=p2)
-        h = conv_op.conv3x3_pair(x1, x2, self.Conv_0.weight, pre=ss, stats=_GN_STATS)
-        return self._fused_tail(h, x1, x2, temb)
+        return self._shortcut_and_tail(h, x1, x2, temb)
 
-    def _fused_tail(self, h, x, x2, temb):
+    def _shortcut_and_tail(self, h, x, x2, temb):
         """(shortcut([x, x2]) + Conv_1(SiLU(GroupNorm_1(h + bias_nc))) + biases) at inference:
         GroupNorm_1+SiLU in Conv_1's input load, the residual in its epilogue, NIN_0's bias
         folded into Conv_1's."""
-        bias_nc = self.Conv_0.bias[None, :].expand(h.shape[0], -1)
-        if temb is not None:
-            bias_nc = bias_nc + temb_proj(self.Dense_0, self.act, temb)
+        bias_nc = conv_temb_bias(self, self.act, temb, h.shape[0])
         bias = self.Conv_1.bias
         if self.in_ch == self.out_ch:
             skip = x if x2 is None else cat_channels(x, x2)  # identity of [x, x2]
-        elif not self.conv_shortcut and _GEMM1X1 and conv_op.gemm1x1_supported(
-                x, self.NIN_0.W.t(), x2):
+        elif not self.conv_shortcut and conv_op.gemm1x1_supported(x, self.NIN_0.W.t(), x2):
             skip = conv_op.conv1x1(x, self.NIN_0.W.t(), None, x2)
             bias = bias + self.NIN_0.b
         else:
             xs = x if x2 is None else cat_channels(x, x2)
             skip = self.Conv_2(xs) if self.conv_shortcut else self.NIN_0(xs)
-        out = gn_silu_conv(h, self.GroupNorm_1, self.Conv_1, bias_nc, bias, skip, 1.0)
-        if out is not None:
-            return out
-        h = gn_act(h, self.GroupNorm_1, self.act, bias_nc)
-        return conv_residual(h, self.Conv_1, bias, skip, 1.0)
+        return inference_tail(self, h, bias_nc, bias, skip, 1.0, stats=False)
 
 
 # ---------------------------------------------------------------- PINN (NCSN-style) blocks
@@ -739,14 +755,10 @@ class ResidualBlock(nn.Module):
         """act(norm(x)); InstanceNorm2d(affine=False) + ELU(1) on the fused HIP kernels
         (op.norm_act.instance_norm_act: forward, backward and double backward one launch
         each, in place of ~30 aten kernels per norm in the PINN residual's double backward).
-        BPK_IN_FUSED=0: aten."""
-        act = self.non_linearity
-        if (_IN_FUSED and x.is_cuda and x.dtype in (torch.float32, torch.float64)
-                and type(norm) is nn.InstanceNorm2d and not norm.affine
-                and not norm.track_running_stats and type(act) is nn.ELU
-                and act.alpha == 1.0 and not act.inplace):
+        _IN_FUSED off: aten."""
+        if self._fused_ok(norm, x):
             return norm_act_op.instance_norm_act(x, norm.eps, norm_act_op.ACT_ELU)
-        return act(norm(x))
+        return self.non_linearity(norm(x))
 
     def forward(self, x):
         if _IN_FANOUT and self._fused_ok(self.normalize1, x) and torch.is_grad_enabled() \
@@ -760,7 +772,7 @@ class ResidualBlock(nn.Module):
         h = self.conv1(a1)
         skip = xs if self.output_dim == self.input_dim else self.shortcut(xs)
         a = self._norm_act(self.normalize2, h)
-        if _RES_TAIL and _is_3x3(a, self.conv2):
+        if _is_3x3(a, self.conv2):
             # skip + conv2(a) with the add in the conv's epilogue (same rounding: the kernel
             # forms conv + bias, then skip + that); its gradient w.r.t. skip is gy itself
             return conv_op.conv3x3(a, self.conv2.weight, self.conv2.bias, skip=skip)

@@ -12,7 +12,6 @@ Per block the arithmetic is re-scheduled for the GPU:
 from __future__ import annotations
 
 import math
-import os
 
 import numpy as np
 import torch
@@ -24,20 +23,14 @@ from op.norm_act import residual_rescale
 
 from . import layers, up_or_down_sampling
 
-# attention at inference: q, k, v as one GEMM over the stacked NIN weights
-_ATTN_QKV = True
-# ... and softmax(q^T k) v as one fused kernel (csrc/attention.hip; False: bmm + softmax + bmm)
-_ATTN_FUSED = True
-# A/B switches of the inference paths outside the 3x3 convs, read once at import:
-# the attention block's residual tail + GroupNorm partials in the NIN_3 GEMM's store
-_GEMM_TAIL = os.environ.get("BPK_GEMM_TAIL", "1") == "1"
-# up blocks: the 1x1 skip projection (Conv_2) before the FIR upsample, on a quarter of the pixels
-_UP_SKIP_FIRST = os.environ.get("BPK_UP_SKIP_FIRST", "1") == "1"
-# up / down blocks: GroupNorm_0 + SiLU applied inside the FIR resampler's loads (upfirdn2d_pre)
-_FIR_PRE = os.environ.get("BPK_FIR_PRE", "1") == "1"
-# up / down blocks: Conv_0 writes its output's GroupNorm partials (no statistics pass for
-# GroupNorm_1)
-_RESAMPLE_STATS = os.environ.get("BPK_RESAMPLE_STATS", "1") == "1"
+# Test seams of the inference paths outside the 3x3 convs: plain constants, all on; a test sets
+# one to False to run the unfused composition beside the fused path.
+_ATTN_FUSED = True      # softmax(q^T k) v as one kernel, False: bmm + softmax + bmm (test_gpu_ops)
+_GEMM_TAIL = True       # attention: residual tail + GroupNorm partials in the NIN_3 GEMM's store
+_UP_SKIP_FIRST = True   # up blocks: the 1x1 skip projection before the FIR upsample
+_FIR_PRE = True         # up / down blocks: GroupNorm_0 + SiLU inside the FIR resampler's loads
+_RESAMPLE_STATS = True  # up / down blocks: Conv_0 writes GroupNorm_1's partial statistics
+# (the last four: test_gpu_resample_block; _FIR_PRE also test_gpu_upfirdn_pre)
 
 conv1x1 = layers.ddpm_conv1x1
 conv3x3 = layers.ddpm_conv3x3
@@ -92,13 +85,12 @@ class AttnBlockpp(nn.Module):
     def forward(self, x):
         h = gn_act(x, self.GroupNorm_0, None)
         div = np.sqrt(2.) if self.skip_rescale else 1.0
-        if _ATTN_QKV and not torch.is_grad_enabled() and self._qkv_ok(h):
+        if not torch.is_grad_enabled() and self._qkv_ok(h):
             return self._forward_qkv(h, x, div)
         h = self.NIN_3(layers._attention(h, self.NIN_0, self.NIN_1, self.NIN_2))
         return residual_rescale(x, h, None, div)
 
     def _qkv_ok(self, h):
-        from op import conv as conv_op
         N, C, H, W = h.shape
         return (h.is_cuda and h.dtype == torch.float32
                 and bool(conv_op.lib.bpk_gemm_nchw_supported(N, 3 * C, H * W, C, 0))
@@ -109,10 +101,9 @@ class AttnBlockpp(nn.Module):
         (op.conv.conv1x1), the 1/sqrt(C) scale folded into q's weights when it is a power of
         two (exact: C = 4^k, e.g. 256) and applied to the logits otherwise.  With `skip` the
         result is the block's output (skip + NIN_3(...)) / div: the residual tail and the
-        output's GroupNorm partial statistics in the NIN_3 GEMM's store (BPK_GEMM_TAIL=0: the
+        output's GroupNorm partial statistics in the NIN_3 GEMM's store (_GEMM_TAIL off: the
         separate residual_rescale launch, no statistics).  The stacked / transposed weights
         are kept between forwards (op.conv.weight_derived)."""
-        from op import conv as conv_op
         B, C, H, W = h.shape
         s = float(int(C) ** (-0.5))
         fold = math.frexp(s)[0] == 0.5  # s is a power of two
@@ -138,7 +129,7 @@ class AttnBlockpp(nn.Module):
         if skip is None:
             return conv_op.conv1x1(out, w3, n3.b)
         if _GEMM_TAIL:
-            return conv_op.conv1x1(out, w3, n3.b, skip=skip, div=div, stats=layers._GN_STATS)
+            return conv_op.conv1x1(out, w3, n3.b, skip=skip, div=div, stats=True)
         return residual_rescale(skip, conv_op.conv1x1(out, w3, n3.b), None, div)
 
 
@@ -279,105 +270,90 @@ class ResnetBlockBigGANpp(nn.Module):
         b1, b2 = self.Conv_1.bias, self.Conv_2.bias
         return conv_op.weight_derived(self, "bias12", [b1, b2], lambda: b1 + b2)
 
+    @property
+    def _div(self):
+        return np.sqrt(2.) if self.skip_rescale else 1.0
+
+    def forward(self, x, temb=None):
+        if not layers.fused_inference_ok(self, x, self.act):
+            return self._autograd(x, temb)
+        if self.up or self.down:
+            return self._inference_resample(x, temb)
+        return self._inference_plain(x, temb)
+
     def forward_pair(self, x1, x2, temb=None):
         """forward(torch.cat([x1, x2], 1), temb) -- the up path's skip concatenation -- at
         inference without building the concatenation: GroupNorm_0 from the parts' partial
-        statistics, Conv_0 reading both sources (Winograd), the 1x1 skip projection as one
-        two-source MFMA GEMM.  Falls back to the concatenation when a piece does not fit."""
-        from op import conv as conv_op
-        from op.norm_act import group_norm_affine_partials
-        C1, C = x1.shape[1], x1.shape[1] + x2.shape[1]
+        statistics, Conv_0 reading both sources (layers.pair_conv0), the 1x1 skip projection as
+        one two-source MFMA GEMM.  Falls back to the concatenation when a piece does not fit."""
+        conv2 = getattr(self, "Conv_2", None)
         ok = (layers.fused_inference_ok(self, x1, self.act) and not (self.up or self.down)
-              and hasattr(self, "Conv_2") and C1 % 8 == 0
-              and x1.dtype == torch.float32 and self.Conv_0.weight.shape[1] == C
-              and bool(conv_op.lib.bpk_conv3x3_wino_supported(
-                  x1.shape[0], C, self.Conv_0.out_channels, x1.shape[2], x1.shape[3]))
-              and conv_op.gemm1x1_supported(x1, self.Conv_2.weight, x2))
-        if ok:
-            # partial statistics of both parts (one read of a part whose producer wrote
-            # none: still cheaper than concatenating and reading the concatenation)
-            p1, p2 = conv_op.ensure_gn_partials(x1), conv_op.ensure_gn_partials(x2)
-            ok = p1 is not None and p2 is not None and p1[1:] == p2[1:]
-        if not ok:
+              and conv2 is not None)
+        h = layers.pair_conv0(self, x1, x2, ok, conv2)
+        if h is None:
             return self.forward(layers.cat_channels(x1, x2), temb)
-        ss = group_norm_affine_partials(p1, x1.shape[0], C, self.GroupNorm_0, part2=p2)
-        h = conv_op.conv3x3_pair(x1, x2, self.Conv_0.weight, pre=ss,
-                                 stats=layers._GN_STATS)
         bias_nc = layers.conv_temb_bias(self, self.act, temb, h.shape[0])
         bias = self._bias12()
-        x = conv_op.conv1x1(x1, self.Conv_2.weight, None, x2)
-        div = np.sqrt(2.) if self.skip_rescale else 1.0
-        out = layers.gn_silu_conv(h, self.GroupNorm_1, self.Conv_1, bias_nc, bias, x, div)
-        if out is not None:
-            return out
-        h = gn_act(h, self.GroupNorm_1, self.act, bias_nc)
-        return layers.conv_residual(h, self.Conv_1, bias, x, div, stats=True)
+        skip = conv_op.conv1x1(x1, self.Conv_2.weight, None, x2)
+        return layers.inference_tail(self, h, bias_nc, bias, skip, self._div, stats=True)
 
-    def forward(self, x, temb=None):
-        fused = layers.fused_inference_ok(self, x, self.act)
-        h = None
-        if fused and not (self.up or self.down):
-            # GroupNorm_0 + SiLU applied inside Conv_0's input load (inference)
-            h = layers.gn_silu_conv(x, self.GroupNorm_0, self.Conv_0)
-        link = None
-        if h is None and not (self.up or self.down):
-            # eval-mode autograd (DPS): the same fusion, its backward recomputing the normalization
-            link = layers.skip_link(self, self.in_ch == self.out_ch
-                                    and layers._dropout_off(self.Dropout_0))
-            r = layers.gn_silu_conv_ad(self, x, self.GroupNorm_0, self.Conv_0, self.act,
-                                       take=link, fanout=self.in_ch != self.out_ch)
-            h = None
-            if r is None:
-                link = None
-            else:
-                h, x = r
-        projected = False
+    def _inference_plain(self, x, temb):
+        """GroupNorm_0 + SiLU applied inside Conv_0's input load"""
+        h = layers.gn_silu_conv(x, self.GroupNorm_0, self.Conv_0)
         if h is None:
-            if (fused and _FIR_PRE and self.fir and (self.up or self.down)
-                    and up_or_down_sampling.resample_2d_pre_supported(x, self.fir_kernel,
-                                                                      self.up)):
-                # inference: GroupNorm_0 + SiLU inside the FIR resampler's loads (the table from
-                # the input's partial statistics when its producer wrote them), no activated
-                # tensor written and read back
-                ss = layers.group_norm_affine(x, self.GroupNorm_0)
-                h = up_or_down_sampling.resample_2d_pre(x, ss, self.fir_kernel, self.up)
-            else:
-                h, x = layers.gn_act_fanout(x, self.GroupNorm_0, self.act)
-                h = self._resample(h)
-            if fused and self.up and _UP_SKIP_FIRST and x.is_cuda:
-                # inference: the 1x1 projection mixes channels, the FIR upsample acts per
-                # channel -- they commute, and projecting first runs the GEMM on a quarter of
-                # the pixels (down blocks project at the low resolution already)
-                x = self._resample(conv_nobias(x, self.Conv_2))
-                projected = True
-            else:
-                x = self._resample(x)
-            if (fused and _RESAMPLE_STATS and layers._GN_STATS
-                    and layers._wino_eligible(h, self.Conv_0)):
-                # GroupNorm_1's statistics from Conv_0's epilogue
-                h = conv_op.conv3x3(h, self.Conv_0.weight, None, stats=True)
-            else:
-                h = conv_nobias(h, self.Conv_0)
+            # a Conv_0 without the prologue form; with grad mode on (and nothing requiring a
+            # gradient) the autograd form of the same fusion is tried next
+            h = layers.gn_silu_conv_ad_1(self, x, self.GroupNorm_0, self.Conv_0, self.act)
+        if h is None:
+            h = self._conv0_stats(gn_act(x, self.GroupNorm_0, self.act))
+        return self._shortcut_and_tail(h, x, temb)
+
+    def _inference_resample(self, x, temb):
+        """FIR up / down block: GroupNorm_0 + SiLU inside the FIR resampler's loads (the table
+        from the input's partial statistics when its producer wrote them), no activated tensor
+        written and read back"""
+        if (_FIR_PRE and self.fir
+                and up_or_down_sampling.resample_2d_pre_supported(x, self.fir_kernel, self.up)):
+            ss = layers.group_norm_affine(x, self.GroupNorm_0)
+            h = up_or_down_sampling.resample_2d_pre(x, ss, self.fir_kernel, self.up)
+        else:
+            h = self._resample(gn_act(x, self.GroupNorm_0, self.act))
+        # the 1x1 projection mixes channels, the FIR upsample acts per channel -- they commute,
+        # and projecting first runs the GEMM on a quarter of the pixels (down blocks project
+        # at the low resolution already)
+        first = self.up and _UP_SKIP_FIRST and x.is_cuda
+        x = self._resample(conv_nobias(x, self.Conv_2) if first else x)
+        return self._shortcut_and_tail(self._conv0_stats(h), x, temb, projected=first)
+
+    def _conv0_stats(self, h):
+        """Conv_0 without bias, GroupNorm_1's statistics from its epilogue"""
+        if _RESAMPLE_STATS and layers._wino_eligible(h, self.Conv_0):
+            return conv_op.conv3x3(h, self.Conv_0.weight, None, stats=True)
+        return conv_nobias(h, self.Conv_0)
+
+    def _shortcut_and_tail(self, h, x, temb, projected=False):
+        """GroupNorm_1 (+ time bias) + SiLU + Conv_1 + residual tail; the 1x1 skip conv's bias
+        joins Conv_1's in the fused residual (no separate full-tensor bias add after the GEMM)"""
         bias_nc = layers.conv_temb_bias(self, self.act, temb, h.shape[0])
         bias = self.Conv_1.bias
-        if self.in_ch != self.out_ch or self.up or self.down:
-            # the 1x1 skip conv's bias joins Conv_1's in the fused residual (no separate
-            # full-tensor bias add after the GEMM)
+        if hasattr(self, "Conv_2"):
             if not projected:
                 x = conv_nobias(x, self.Conv_2)
-            bias = self._bias12() if fused else bias + self.Conv_2.bias
-        div = np.sqrt(2.) if self.skip_rescale else 1.0
-        if fused:
-            # GroupNorm_1 (+ time bias) + SiLU + Conv_1 + residual tail: two launches
-            out = layers.gn_silu_conv(h, self.GroupNorm_1, self.Conv_1, bias_nc, bias, x, div)
-            if out is not None:
-                return out
-        elif layers._dropout_off(self.Dropout_0):
-            out = layers.gn_silu_conv_ad_1(self, h, self.GroupNorm_1, self.Conv_1, self.act,
-                                           bias_nc=bias_nc, conv_bias=bias, skip=x, div=div,
-                                           give=link)
-            if out is not None:
-                return out
-        h = gn_act(h, self.GroupNorm_1, self.act, bias_nc)
-        h = self.Dropout_0(h)
-        return layers.conv_residual(h, self.Conv_1, bias, x, div, stats=fused)
+            bias = self._bias12()
+        return layers.inference_tail(self, h, bias_nc, bias, x, self._div, stats=True)
+
+    def _autograd(self, x, temb):
+        """training, and eval-mode gradients (DPS): there the plain block's convs take the fused
+        first-order Function, its backward recomputing the normalization"""
+        if self.up or self.down:
+            h, x = layers.gn_act_fanout(x, self.GroupNorm_0, self.act)
+            h, x = self._resample(h), self._resample(x)
+            h, link = conv_nobias(h, self.Conv_0), None
+        else:
+            h, x, link = layers.autograd_conv0(self, x)
+        bias_nc = layers.conv_temb_bias(self, self.act, temb, h.shape[0])
+        bias = self.Conv_1.bias
+        if hasattr(self, "Conv_2"):
+            x = conv_nobias(x, self.Conv_2)
+            bias = bias + self.Conv_2.bias
+        return layers.autograd_tail(self, h, bias_nc, bias, x, self._div, link)

@@ -19,10 +19,6 @@ from op.norm_act import residual_rescale
 
 from . import layers, layerspp, utils
 
-# up-path skip concatenations read as two sources at inference (False: torch.cat)
-_PAIR = True
-# all residual blocks' time-embedding projections as one GEMM at inference
-_TEMB_BANK = True
 conv3x3 = layerspp.conv3x3
 default_initializer = layers.default_init
 _SQRT2 = np.sqrt(2.)
@@ -214,8 +210,8 @@ class NCSNpp(nn.Module):
     def forward(self, x, time_cond):
         mods = self.all_modules
         temb, used_sigmas = self._time_embedding(time_cond)
-        if temb is not None and _TEMB_BANK and x.is_cuda and (
-                layers._TEMB_BANK_AD or layers.fused_inference_ok(self, x, self.act)):
+        if temb is not None and x.is_cuda:
+            # every block's Dense_0 projection of act(temb) as one GEMM (layers.TembBank)
             if self._denses is None:
                 blocks = [m for m in self.all_modules
                           if hasattr(m, "Dense_0") and isinstance(m.Dense_0, nn.Linear)]
@@ -259,7 +255,8 @@ class NCSNpp(nn.Module):
                 h = hs[-1]
             elif kind == "res_cat":
                 blk = mods[step[1]]
-                if hasattr(blk, "forward_pair") and _PAIR:
+                if hasattr(blk, "forward_pair"):
+                    # the skip concatenation read as two sources at inference
                     h = blk.forward_pair(h, hs.pop(), temb)
                 else:
                     h = blk(layers.cat_channels(h, hs.pop()), temb)

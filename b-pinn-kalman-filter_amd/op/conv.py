@@ -108,8 +108,8 @@ def refresh_filters(registry: list):
             registry[i] = (weight, U, ft, weight._version, form)
 
 
-# BPK_WEIGHT_CACHE=0: weight-only tensors are rebuilt by every forward; read once at import
-_WEIGHT_CACHE = os.environ.get("BPK_WEIGHT_CACHE", "1") == "1"
+# test seam (test_gpu_resample_block): False rebuilds weight-only tensors in every forward
+_WEIGHT_CACHE = True
 
 
 def weight_derived(owner, key, params, build):
@@ -1353,7 +1353,7 @@ def up2_supported(x, weight):
     return bool(lib.bpk_conv3x3_wino_up2_supported(N, C, weight.shape[0], 2 * H, 2 * W))
 
 
-_WINO_UP2 = True
+_WINO_UP2 = True  # test seam (test_gpu_ops): False sends layers.Upsample to interpolate + conv
 
 
 def _up2_raw(x, weight, bias):

@@ -1,6 +1,6 @@
 """Verdict over the outputs of trace_launches.py:
 
-    python profiles/conv_autograd_unify/compare_traces.py parent1.pt branch1.pt parent2.pt branch2.pt ...
+    python tools/compare_traces.py parent1.pt branch1.pt parent2.pt branch2.pt ...
 
 Traces are compared per workload (the first word of each line); where two differ, every line
 that is in one and not in the other is printed.  Tensors: how many are torch.equal, and the

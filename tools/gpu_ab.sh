@@ -3,8 +3,8 @@
 #   tools/gpu_ab.sh OUT VAR "VALUES" REPEATS [bench.py args...]
 # e.g. tools/gpu_ab.sh OUT BPK_GN_FANOUT "0 1" 2 --full --no-pinn --no-dps --ns-steps 0 \
 #        --ncddpmpp-steps 0 --no-cpu-baseline --no-roofline --train-steps 8 --cifar-steps 6
-# The round's switches: BPK_DEFER_WGRAD, BPK_GN_FANOUT, BPK_IN_FANOUT, BPK_PINN_COPIES,
-# BPK_GN_CONV_AD_TRAIN.  Each run's JSON line goes to OUT/<VAR>_<value>_<repeat>.json and
+# The environment switches: BPK_DEFER_WGRAD, BPK_GN_FANOUT, BPK_GN_CONV_AD, BPK_PINN_COPIES,
+# BPK_BAYES_FUSED, BPK_WINO_F24.  Each run's JSON line goes to OUT/<VAR>_<value>_<repeat>.json and
 # every "*_per_s" rate of it is printed.
 set -o pipefail
 O=$1; VAR=$2; VALS=$3; REP=$4; shift 4

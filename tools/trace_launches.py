@@ -2,11 +2,18 @@
 argument, null / non-null for each pointer argument, the returned status or byte count), per
 workload, plus the tensors each workload produced.
 
-    BPK_CONV_PICK=first python profiles/conv_autograd_unify/trace_launches.py ROOT OUT.pt
+    BPK_CONV_PICK=first python tools/trace_launches.py ROOT OUT.pt
 
 ROOT: the repository root to trace (this tree, or an export of the parent commit; BPK_LIB names
 the libbpk.so when ROOT has none built).  One fresh process per run; compare_traces.py reads
-the OUT files."""
+the OUT files.
+
+Workloads: one training step per train fixture (`train_*`), a DPS-style input gradient through
+`ncsnpp_a` (`dps_*`), the same inside `higher_order_autograd()` (`higher_*`), one `no_grad`
+forward of every net fixture (`infer_*`), one forward of `ncsnpp_a` with grad enabled and all
+parameters frozen (`frozen_*`), one eager PINN training step (`pinn`), and a double backward
+outside `deferred_weight_grads()` (`nodefer`)."""
+import contextlib
 import ctypes
 import os
 import sys
@@ -113,6 +120,28 @@ def dps_input_gradient(name="ncsnpp_a"):
     keep("gx", gx)
 
 
+def higher_order_input_gradient(name="ncsnpp_a"):
+    from models import layers
+    SECTION[0] = f"higher_{name}"
+    _, model, x, labels = score_model(name)
+    x = torch.tensor(x, device=hip).requires_grad_()
+    with layers.higher_order_autograd():
+        out = model(x, torch.tensor(labels, device=hip))
+        gx, = torch.autograd.grad((out ** 2).sum(), x)
+    keep("out", out)
+    keep("gx", gx)
+
+
+def inference(name, frozen=False):
+    """one forward without an autograd graph: under no_grad, or (frozen) with grad enabled and
+    no parameter requiring a gradient"""
+    SECTION[0] = f"{'frozen' if frozen else 'infer'}_{name}"
+    _, model, x, labels = score_model(name)
+    with contextlib.nullcontext() if frozen else torch.no_grad():
+        keep("out", model.requires_grad_(not frozen)(torch.tensor(x, device=hip),
+                                                     torch.tensor(labels, device=hip)))
+
+
 def pinn_step(batch=4):
     """one eager training step of the shipped PINN configuration (deferred weight gradients)"""
     import losses
@@ -178,6 +207,10 @@ def double_backward_not_deferred():
 for name in ("dsm_ncsnpp", "dsm_fourier", "ddpm_discrete"):
     train_step(name)
 dps_input_gradient()
+higher_order_input_gradient()
+for name in ("ncsnpp_a", "ncsnpp_b", "ncsnpp_c", "ddpm_a"):
+    inference(name)
+inference("ncsnpp_a", frozen=True)
 pinn_step()
 double_backward_not_deferred()
 torch.cuda.synchronize()
